@@ -25,21 +25,26 @@ Which model (when --model is not given):
               fp8 / int8 / mask24        -> Mixtral-8x7B (configs[3]; 896 tensors, 92.9 GB: 11.6 GB per rank at N = 8)
               int4g128 / mxfp4 / mxfp4-sq -> Llama-3-70B (configs[4]; 560 tensors, 136.9 GB: 17.1 GB per rank at N = 8)
             Both fit ONE MI355X in place, so `--model mixtral-8x7b` / `--model llama3-70b` at N = 1 is the base of that
-            curve; the default N = 1 line carries it as extra.scale_base_n1 (same step, same model, one GPU).
+            curve; the --full N = 1 line carries it as extra.scale_base_n1 (same step, same model, one GPU).
             `--scaling weak` (every rank holds one model's worth; the pool grows with N) is kept as a switch and the
-            weak leg of the default run is reported in extra.weak_scaling -- it is not a BASELINE configuration.
+            weak leg of a --full run is reported in extra.weak_scaling -- it is not a BASELINE configuration.
 
-`extra` (rank 0, outside the timed region) carries the other half of BASELINE.json's metric and the north-star
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it builds the pool, ramps,
+warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the line (`value`,
+`ms_per_step`, `roofline` from the events of the timed launches).  Everything below -- the node probe, `extra`, the CPU
+baseline -- runs only with `--full`.
+
+`extra` (--full; rank 0, outside the timed region) carries the other half of BASELINE.json's metric and the north-star
 target: the INT4-AWQ PTQ wall-clock of the full synthetic Llama-3-8B (tools/awq_bench.py, calibration batches sharded
 over the ranks) and, at N = 1, the fused per-group amax + INT4 QDQ kernel over all Llama-3-70B weights in place.
 The CPU baseline runs LAST and in a process of its own (`--cpu-baseline-only`): its OpenMP runtime never shares a
 process with a timed flow.
 
 Contract: python bench.py --gpus N --steps K --warmup W ; one JSON line on rank 0.  `--gpus N` without a launcher
-(no WORLD_SIZE in the environment) re-executes itself under `python -m torch.distributed.run --nnodes=1
---nproc-per-node N --master-addr 127.0.0.1`; under torchrun (the driver's form) it runs as the rank it is.
+(no WORLD_SIZE in the environment) runs itself again under `python -m torch.distributed.run --nnodes=1
+--nproc-per-node N --master-addr 127.0.0.1` as a child process; under torchrun (the driver's form) it runs as the rank it is.
 
-RULE: no edit of this file ships without ONE full default run (`python bench.py --gpus 1 --steps 20 --warmup 5`, all
+RULE: no edit of this file ships without ONE full default run (`python bench.py --gpus 1 --steps 20 --warmup 5 --full`, all
 extras) after it, its line committed under profiles/ -- round 3 shipped an order change that was only ever run with
 shortened extras and the driver's AWQ figure came out 2.4x the claimed one.
 """
@@ -99,14 +104,17 @@ def make_weights(model, n_layers, device, seed=1234, rank=0, world=1, scaling="s
     g = torch.Generator(device=device)
     ws, idx = [], []
     for i in mine:
-        shape = shapes[i]
-        g.manual_seed(seed + i)
-        w = torch.randn(shape, generator=g, device=device, dtype=torch.float32) * 0.02
-        m = torch.rand(shape, generator=g, device=device) < 0.001
-        ws.append(torch.where(m, w * 8, w).to(torch.bfloat16))
+        ws.append(pool_weight(shapes[i], i, device, g, seed))
         idx.append(i)
-        del w, m
     return ws, idx, len(shapes)
+
+
+def pool_weight(shape, i, device, g, seed=1234):
+    """Tensor i of the pool: bf16 N(0, 0.02^2) with 0.1% x8 outliers, seeded by its pool index."""
+    g.manual_seed(seed + i)
+    w = torch.randn(shape, generator=g, device=device, dtype=torch.float32) * 0.02
+    m = torch.rand(shape, generator=g, device=device) < 0.001
+    return torch.where(m, w * 8, w).to(torch.bfloat16)
 
 
 PMC_KERNEL = {"fp8": "mt_map_kernel<2, moq::OpFp8Qdq>", "int8": "mt_map_kernel<2, moq::OpIntQdq>",
@@ -364,8 +372,14 @@ def launch_command(n, argv, port=None):
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the node probe, the secondary measurements (other kernels, "
+                         "pools and flows) and the CPU baseline.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of the weights, group amax and masks, every per-tensor amax)")
     ap.add_argument("--workload", default="fp8", choices=["fp8", "int4g128", "int8", "mxfp4", "mxfp4-sq", "mask24", "fp8-mask24"])
     ap.add_argument("--model", default=None, choices=list(MODELS),
                     help="default: llama3-8b at N = 1 (BASELINE configs[1]); at N > 1 the multi-GPU configuration of the "
@@ -384,7 +398,7 @@ def build_parser():
                          "the only form in which llama3-70b fits one GPU.  The default line carries the out-of-place time "
                          "of the same launch in extra.qdq_out_of_place")
     ap.add_argument("--inplace", action="store_true", help="(accepted for old command lines; in place is the default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-node-probe", action="store_true",
                     help="skip the 2 GiB probe launches after the timed region (tools/profile_bench.sh: the profiled process "
                          "then launches the dominant kernel on the workload's tensors only, so rocprofv3's per-kernel "
@@ -394,7 +408,7 @@ def build_parser():
                          "process the main run starts for it, last")
     ap.add_argument("--cpu-baseline-inproc-first", action="store_true",
                     help="DIAGNOSTIC (round 3's order): time the CPU baseline inside this process BEFORE the AWQ extras")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (other kernels, the "
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the secondary measurements (other kernels, the "
                                                             "Llama-3-70B in-place pass, the INT4-AWQ wall-clock)")
     ap.add_argument("--no-hf", action="store_true", help="extra: skip the INT4-AWQ flow on the random-init HF Llama-3-8B")
     ap.add_argument("--awq-layers", type=int, default=32, help="extra: layers of the INT4-AWQ wall-clock run (0 = skip)")
@@ -412,6 +426,7 @@ class Pool:
 
         self.moa, self.wl, self.dev, self.use_dist = moa, wl, dev, use_dist
         self.weights, owned, self.n_tensors = make_weights(model, n_layers, dev, rank=rank, world=world, scaling=scaling)
+        self.owned = owned
         self.n_local = sum(w.numel() for w in self.weights)
         self.n_model_elem = sum(r * c for _ in range(n_layers) for r, c in layer_shapes(model))  # one model
         self.weak = scaling == "weak" and world > 1
@@ -450,6 +465,14 @@ class Pool:
             self.masks = [torch.empty(w.shape, dtype=torch.bool, device=dev) for w in self.weights]
             self.mask_tab = SegmentTable(self.weights, outputs=self.masks)
         self.dom_events = []
+
+    def reset(self):
+        """Every weight back to its seeded initial values, in place (the segment tables keep their pointers), and the
+        fold alternation back to its first side: the steps that follow start from the same state in every run."""
+        g = torch.Generator(device=self.dev)
+        for w, i in zip(self.weights, self.owned):
+            w.copy_(pool_weight(w.shape, i, self.dev, g))
+        self.step_no = 0
 
     def release(self):
         self.tab = self.groups = self.weights = self.masks = self.mask_tab = self.fold_scales = self.fold_sides = None
@@ -534,8 +557,8 @@ class Pool:
             stop()
 
     def run(self, steps, warmup, ramp_s=1.5):
-        """Ramp (untimed), `warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides;
-        returns the elapsed seconds, MAX over the ranks."""
+        """Ramp (untimed), the weights reset to their seeded values, `warmup` untimed steps, then exactly `steps` steps
+        between barrier + synchronize on both sides; returns the elapsed seconds, MAX over the ranks."""
         import torch.distributed as dist
 
         # Power-state ramp (not a measured step, not part of the W warm-up steps): a GPU that has been idle starts a
@@ -547,6 +570,9 @@ class Pool:
         while time.perf_counter() - t_ramp < ramp_s:
             self.step(False, collective=False)
             torch.cuda.synchronize()
+        # the in-place steps rewrite the weights and the ramp's count varies: warm-up and timed steps start from the seeded
+        # weights, so the last step's inputs and outputs are the same from run to run (--dump-outputs)
+        self.reset()
         for _ in range(warmup):
             self.step(False)
 
@@ -573,18 +599,66 @@ class Pool:
         return elapsed
 
 
+def sample_segments(tensors, pool_idx, k_total, seed=4321):
+    """A fixed sample of k_total elements (about) of a list of tensors, as one float32 array: tensor i contributes a share
+    proportional to its size, at positions drawn from a generator seeded by its pool index (the same positions in every
+    run and on every rank); everything when the tensors hold no more than k_total elements."""
+    n_all = sum(t.numel() for t in tensors)
+    parts = []
+    for t, i in zip(tensors, pool_idx):
+        flat = t.reshape(-1)
+        if n_all <= k_total:
+            parts.append(flat.float().cpu())
+            continue
+        k = max(1, round(k_total * flat.numel() / n_all))
+        pos = torch.randint(flat.numel(), (k,), generator=torch.Generator().manual_seed(seed + i))
+        parts.append(flat[pos.to(flat.device)].float().cpu())
+    return torch.cat(parts).numpy()
+
+
+def dump_outputs(pool, outdir):
+    """What the last timed step handed its caller, as <outdir>/<name>.npy in float32 (under 49 MiB in all):
+    weights = the quantized weights (the step's outputs, in place), amax = the per-tensor abs-max (per-group for int4g128),
+    masks = the 2:4 masks, amax_all = every rank's per-tensor abs-max after the all-reduce (N > 1)."""
+    import numpy as np
+
+    wl, tab = pool.wl, pool.tab
+    arrays = {}
+    if wl != "mask24":  # (mask24 writes the masks only)
+        arrays["weights"] = sample_segments(tab.outputs, pool.owned, 8 << 20)
+    if wl in ("mask24", "fp8-mask24"):
+        arrays["masks"] = sample_segments(pool.mask_tab.outputs, pool.owned, 4 << 20)
+    if wl == "int4g128":
+        arrays["amax"] = sample_segments(tab.amax, pool.owned, 2 << 20)
+    elif wl in ("fp8", "int8", "fp8-mask24"):
+        amax = (torch.cat([gt.amax_flat for gt in pool.groups]) if pool.groups is not None else tab.amax_flat)
+        arrays["amax"] = amax.float().cpu().numpy()
+        if pool.use_dist:
+            arrays["amax_all"] = pool.amax_all.float().cpu().numpy()
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), a.astype(np.float32, copy=False))
+
+
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.workload)), flush=True)
         return
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run measures the headline only: no node probe, no secondary measurements, no CPU baseline
+        args.no_extra = args.no_cpu_baseline = args.no_node_probe = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # the contract command without a launcher: become the launcher (one rank per GPU; MOQ_BENCH_DEBUG_ONE_GPU=1 puts
-        # all ranks on cuda:0 over gloo).  exec: the launcher's exit code and rank 0's stdout are this command's.
-        cmd = launch_command(args.gpus, sys.argv[1:])
+        # the contract command without a launcher: start the launcher as a child (one rank per GPU; MOQ_BENCH_DEBUG_ONE_GPU=1
+        # puts all ranks on cuda:0 over gloo).  The launcher's exit code and rank 0's stdout are this command's.
+        import subprocess
+
         sys.stdout.flush()
-        os.execv(cmd[0], cmd)
+        sys.exit(subprocess.run(launch_command(args.gpus, sys.argv[1:])).returncode)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -647,6 +721,8 @@ def main():
     weights, tab, masks = pool.weights, pool.tab, pool.masks
     n_local, n_model_elem, n_elem, n_tensors, weak = pool.n_local, pool.n_model_elem, pool.n_elem, pool.n_tensors, pool.weak
     elapsed = pool.run(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pool, args.dump_outputs)
     ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
 
     ms_per_step = elapsed / args.steps * 1e3

@@ -4,6 +4,7 @@ two scaling modes, the model shape tables behind the metric's byte counts, and t
 import importlib.util
 import os
 
+import numpy as np
 import pytest
 import torch
 
@@ -78,7 +79,7 @@ def test_default_model_is_the_baseline_config_of_the_format():
 
 
 def test_bare_contract_command_launches_its_own_ranks():
-    """`python bench.py --gpus 2` with no launcher in the environment re-executes itself under torch.distributed.run:
+    """`python bench.py --gpus 2` with no launcher in the environment starts itself again under torch.distributed.run:
     here (no GPU) both ranks then stop with the no-GPU message -- which only ranks started by the launcher print twice."""
     import subprocess
     import sys
@@ -158,3 +159,64 @@ def test_scale_n_builds_the_drivers_command_lines_and_refuses_lines_that_are_not
     assert any("no `collective`" in p for p in scale_n.check_line(dict(line, collective=None), 2))
     assert any("n_gpus" in p for p in scale_n.check_line(dict(line, n_gpus=1), 2))
     assert any("missing field roofline" in p for p in scale_n.check_line({k: v for k, v in line.items() if k != "roofline"}, 2))
+
+
+def test_plain_run_is_the_headline_only_and_full_brings_back_the_rest():
+    """A plain run carries no node probe, secondary measurements or CPU baseline; `--full` is off by default; --steps sets
+    the timed steps and must be at least 1."""
+    args = bench.build_parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 2)
+    args = bench.build_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert args.full and args.dump_outputs == "d"
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert "args.no_extra = args.no_cpu_baseline = args.no_node_probe = True" in src
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def _tensors(shapes, seed=5):
+    g = torch.Generator().manual_seed(seed)
+    return [(torch.randn(shape, generator=g) * 0.02).to(torch.bfloat16) for shape in shapes]
+
+
+def test_dump_samples_are_fixed_and_bounded():
+    """sample_segments: everything when the tensors are small, otherwise a share per tensor at positions seeded by its pool
+    index -- the same positions in every run."""
+    ws, idx = _tensors([(256, 512), (128, 512), (512, 256)]), [3, 7, 11]
+    small = bench.sample_segments([w[:4] for w in ws], idx, 1 << 20)
+    assert small.dtype == np.float32 and np.array_equal(small, torch.cat([w[:4].reshape(-1).float() for w in ws]).numpy())
+    a = bench.sample_segments(ws, idx, 100_000)
+    assert a.dtype == np.float32 and abs(a.size - 100_000) <= 3
+    assert np.array_equal(a, bench.sample_segments(ws, idx, 100_000))
+    assert np.isin(a, torch.cat([w.reshape(-1).float() for w in ws]).numpy()).all()
+    assert not np.array_equal(a, bench.sample_segments(ws, [4, 8, 12], 100_000))  # positions follow the pool index
+
+
+@pytest.mark.parametrize("wl", ["fp8", "int8", "int4g128", "mxfp4", "mxfp4-sq", "mask24", "fp8-mask24"])
+def test_dump_outputs_writes_what_the_step_returns(wl, tmp_path):
+    """dump_outputs on a stand-in pool of CPU tensors: float32 .npy files named after what the step hands its caller."""
+    from types import SimpleNamespace
+
+    ws, idx = _tensors([(64, 256), (32, 256), (64, 128)]), [0, 1, 2]
+    masks = [torch.rand(w.shape, generator=torch.Generator().manual_seed(i)) < 0.5 for i, w in enumerate(ws)]
+    amax = torch.stack([w.float().abs().max() for w in ws])
+    gam = torch.cat([w.float().abs().reshape(-1, 128).amax(1) for w in ws])
+    tab = SimpleNamespace(outputs=ws, amax_flat=gam if wl == "int4g128" else amax,
+                          amax=list(gam.split([w.numel() // 128 for w in ws])))
+    pool = SimpleNamespace(wl=wl, tab=tab, owned=idx, groups=None, use_dist=False, amax_all=None,
+                           mask_tab=SimpleNamespace(outputs=masks) if wl in ("mask24", "fp8-mask24") else None)
+    bench.dump_outputs(pool, str(tmp_path / "d"))
+    want = {"fp8": {"weights", "amax"}, "int8": {"weights", "amax"}, "int4g128": {"weights", "amax"}, "mxfp4": {"weights"},
+            "mxfp4-sq": {"weights"}, "mask24": {"masks"}, "fp8-mask24": {"weights", "masks", "amax"}}[wl]
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert set(got) == want and all(a.dtype == np.float32 for a in got.values())
+    if "weights" in got:
+        assert np.array_equal(got["weights"], torch.cat([w.reshape(-1).float() for w in ws]).numpy())
+    if "masks" in got:
+        assert np.array_equal(got["masks"], torch.cat([m.reshape(-1).float() for m in masks]).numpy())
+    if "amax" in got:
+        assert np.array_equal(got["amax"], tab.amax_flat.numpy())

@@ -517,6 +517,32 @@ int moq_awq_quadform(const void* a, const void* b, const float* ref, int64_t row
 int moq_block2d(const void* x, void* y, float* amax, int64_t rows, int64_t cols, int br, int bc, int dt, int mode,
                 int accumulate, int fp8, int num_bits, int is_unsigned, int narrow_range, void* stream);
 
+/* ------------------------------------------------------------------ static NVFP4 weights (E2M1, E4M3 block scales) */
+
+/* Static two-level FP4 QDQ over n_blocks consecutive blocks of `block` (= 16) elements -- static_blockwise_fp4_fake_quant
+ * with quantize_block_scales=True and fp8_max_for_normalization=448 (kernels/quantization/gemm/fp4_kernel.py:217-318):
+ * s_b = fp8_eager(amax[b] / 6, global_amax[0] / 6) (compute_fp4_scales, tensor_quant.py:46-59), then
+ * y = (x >= 0 ? 1 : -1) * q(|x| / s_b) * s_b with q = fp4_round_magnitude (round half to even onto {0, .5, 1, 1.5, 2, 3, 4, 6},
+ * saturating; a NaN quotient gives 6); a zero s_b gives a +0 block, a NaN / infinite s_b is replaced by 1
+ * (nvfp4_scalar_quant, common/nvfp4_quant.py).  amax: fp32 [n_blocks]; x, y 16-byte aligned; x == y allowed. */
+int moq_nvfp4_static_qdq(const void* x, void* y, const float* amax, const float* global_amax, int64_t n_blocks,
+                         int block, int dt, void* stream);
+/* FP8 block-scale sweep (_fp8_scale_sweep_kernel, gemm/nvfp4_fp8_sweep.py:59-124): for every block and every candidate
+ * c_k = e4m3_k / 448 (the 126 positive finite E4M3 values, ascending; _fp8_scale_candidates.py) with
+ * s_k = fl(fl(c_k * g) / 6) (1 where that is 0), loss_k = sum_i (|w_i| - fl(q(fl(|w_i| / s_k)) * s_k))^2 in fp32 with the 16
+ * terms summed as r_j = p_j + p_{j+8}, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)); the first strict minimum wins;
+ * best_amax[b] = fl(c_best * g).  g = global_amax[0].  x: [n_blocks, block] (block = 16), 16-byte aligned. */
+int moq_nvfp4_fp8_sweep(const void* x, const float* global_amax, float* best_amax, int64_t n_blocks, int block, int dt,
+                        void* stream);
+/* Hessian-weighted sweep (_fp8_scale_sweep_hessian_kernel, gemm/nvfp4_fp8_sweep.py:174-226): as moq_nvfp4_fp8_sweep with
+ * candidate scales from compute_fp4_scales(fl(c_k * g), g) (the FP8 round trip included; 1 where 0) and the loss
+ * dw^T H_n dw, dw_i = (w_i >= 0 ? 1 : -1) * (|w_i| - fl(q * s_k)), H_n = hessian[n] (fp32 [16, 16]) of the block's
+ * cin-block n = b % n_cin_blocks.  (dw H)_j is the fmaf chain over k = 0,4,8,12, 1,5,9,13, 2,6,10,14, 3,7,11,15 from +0
+ * (v_mfma_f32_16x16x4_f32), the 16 products fl((dw H)_j * dw_j) are summed as in moq_nvfp4_fp8_sweep.
+ * best_amax[b] = fl(c_best * g).  n_blocks % n_cin_blocks != 0 (cin % 16 != 0) -> MOQ_ERR_UNSUPPORTED. */
+int moq_nvfp4_fp8_sweep_hessian(const void* x, const float* hessian, const float* global_amax, float* best_amax,
+                                int64_t n_blocks, int64_t n_cin_blocks, int block, int dt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

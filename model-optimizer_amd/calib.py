@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, numerics, ops
+from ._lib import MoquantUnsupported
 
 
 class _Calibrator:
@@ -897,3 +898,43 @@ class MseCalibrator(_Calibrator):
         best = torch.argmin(losses, dim=0)
         self._amax = self._compute_candidate_amax(self._candidates[best])
         return self._amax
+
+
+class NVFP4MSECalibrator(_Calibrator):
+    """Per-block FP8 scale sweep of a static NVFP4 weight quantizer -- calib/mse.py:175-310.  One-shot: `collect` takes the
+    weight in its blocked [n_blocks, 16] layout and runs ONE kernel over the 126 E4M3 candidates (the Hessian-weighted one
+    when `hessian` [cin // 16, 16, 16] is given, for local_hessian); `compute_amax` returns the chosen block amax in the
+    shape of the initial amax.  `reset` keeps `_initial_amax`, so the calibrator can run again."""
+
+    def __init__(self, amax, global_amax, axis=None, quant_func=None, error_func=None, hessian=None):
+        super().__init__(num_bits=None, axis=axis, unsigned=None)
+        self._initial_amax = amax
+        self._global_amax = torch.as_tensor(global_amax).detach().to(dtype=torch.float32)
+        self._quant_func, self._error_func = quant_func, error_func
+        self._hessian = hessian
+        self._best_amax = None
+
+    @torch.no_grad()
+    def collect(self, x: torch.Tensor):
+        if self._best_amax is not None:
+            raise RuntimeError("NVFP4MSECalibrator: a previous collect() call produced a final amax; multi-collect is not "
+                               "supported. Call reset() to start a fresh cycle.")
+        if x.dim() != 2 or x.shape[0] != self._initial_amax.numel():
+            raise MoquantUnsupported(f"NVFP4MSECalibrator: the input must be the blocked [n_blocks, block] layout of the "
+                                     f"{self._initial_amax.numel()} block amax values (got {tuple(x.shape)})")
+        if self._error_func is not None and self._hessian is None:
+            # the reference's Python sweep with a custom metric (mse.py:289-297) has no kernel here
+            raise MoquantUnsupported("NVFP4MSECalibrator: a custom error function without a Hessian")
+        ga = self._global_amax.to(x.device)
+        if self._hessian is not None:
+            best = ops.nvfp4_fp8_scale_sweep_hessian(x, ga, self._hessian, block_size=x.shape[-1])
+        else:
+            best = ops.nvfp4_fp8_scale_sweep(x, ga, block_size=x.shape[-1])
+        self._best_amax = best.reshape(self._initial_amax.shape).to(dtype=torch.float32)
+
+    @torch.no_grad()
+    def compute_amax(self, verbose: bool = False):
+        return self._best_amax
+
+    def reset(self):
+        self._best_amax = None

@@ -305,16 +305,69 @@ def promote_static_block_weight_quantizers(model: nn.Module) -> int:
     StaticBlockScaleQuantizer).  Later amax writes (MSE refinement, AWQ re-calibration) are then not rounded to
     the weight dtype."""
     n = 0
-    for m in model.modules():
+    nvfp4 = {}
+    for name, m in model.named_modules():
         if not is_quantized_linear(m):
             continue
         wq = m.weight_quantizer
         if isinstance(wq, SequentialQuantizer):
             continue
+        if wq.is_enabled and wq.is_nvfp4_static and wq.amax is not None:
+            nvfp4[name] = wq
+            if not getattr(wq, "_is_static_block_scale_quantizer", False):
+                wq.promote_static_block()
+                n += 1
+            continue
         if (wq.is_enabled and wq.is_static_block_quant and wq.amax is not None and isinstance(wq._num_bits, int)
                 and not getattr(wq, "_is_static_block_scale_quantizer", False)):
             wq.promote_static_block()
             n += 1
+    _set_nvfp4_global_amax(nvfp4)
+    return n
+
+
+# the linears that read one input and are fused at deployment share one NVFP4 global amax (utils/shared_input.py:58-62,
+# core_utils.py:1095-1150): siblings under one parent module
+NVFP4_SHARED_SIBLINGS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"), ("w1", "w3"))
+
+
+def _set_nvfp4_global_amax(quantizers: dict) -> None:
+    """global_amax = max of the per-block amax (StaticBlockScaleQuantizer.from_tensor_quantizer, :1531-1546), the max over
+    the group for fusible siblings."""
+    groups: dict = {}
+    for name, wq in quantizers.items():
+        parent, _, leaf = name.rpartition(".")
+        key = next(((parent, i) for i, g in enumerate(NVFP4_SHARED_SIBLINGS) if leaf in g), name)
+        groups.setdefault(key, []).append(wq)
+    for members in groups.values():
+        g = torch.stack([wq._amax.float().max().to(members[0]._amax.device) for wq in members]).max()
+        for wq in members:
+            wq.global_amax = g
+
+
+def _nvfp4_sweep_weights(model: nn.Module, hessian_for=None) -> int:
+    """The FP8 scale sweep of every static NVFP4 weight quantizer (_make_weight_mse_calibrator with fp8_scale_sweep,
+    model_calib.py:670-730): NVFP4MSECalibrator over the weight's blocks, one kernel per weight; every other weight keeps
+    its max-calibrated amax.  hessian_for(quantizer) -> normalised per-block Hessian [cin // 16, 16, 16] or None."""
+    from .calib import NVFP4MSECalibrator
+
+    n = 0
+    for m in model.modules():
+        if not is_quantized_linear(m):
+            continue
+        wq = m.weight_quantizer
+        if (not isinstance(wq, TensorQuantizer) or not wq.is_enabled or not wq.is_nvfp4_static
+                or getattr(wq, "_amax", None) is None or wq.global_amax is None):
+            continue
+        w = m.weight
+        wq._setup_for_blockquant(w)
+        blocks = wq._process_for_blockquant(w.detach())
+        h = hessian_for(wq) if hessian_for is not None else None
+        cal = NVFP4MSECalibrator(amax=wq._amax.clone().detach(), global_amax=wq.global_amax, axis=wq._axis, hessian=h)
+        cal.collect(blocks)
+        wq.amax = cal.compute_amax()
+        cal.reset()
+        n += 1
     return n
 
 
@@ -347,11 +400,14 @@ def mse_calibrate(model: nn.Module, forward_loop=None, distributed_sync: bool = 
                   shared_states=None):
     """model_calib.py:732-826 (multiplier search, fp8_scale_sweep=False): max calibration first, then every
     eligible weight quantizer's amax is refined by the MSE sweep -- here one fused kernel per weight."""
-    if fp8_scale_sweep or shared_states:
-        # the FP8-scale sweep of NVFP4 static block scales and shared quantizer state (model_calib.py:740-741, :770-826)
-        # belong to formats outside this path; the reference's defaults (False / None) are accepted
-        raise MoquantUnsupported("mse_calibrate: fp8_scale_sweep / shared_states are outside this path")
+    if shared_states:
+        # shared quantizer state other than the default sibling groups (model_calib.py:770-826) is outside this path
+        raise MoquantUnsupported("mse_calibrate: shared_states are outside this path")
     max_calibrate(model, forward_loop, distributed_sync)
+    if fp8_scale_sweep:
+        # only static NVFP4 weights are searched (the FP8 scale sweep); every other weight stays at max (:695-718)
+        _nvfp4_sweep_weights(model)
+        return
     _mse_calibrate_weights(model, step_size, start_multiplier, stop_multiplier)
 
 
@@ -516,9 +572,20 @@ def local_hessian_calibrate(model: nn.Module, forward_loop=None, distributed_syn
         warnings.warn("local_hessian: Hessian is not synced across ranks; refined weight amaxes may diverge under "
                       "tensor/data parallelism. Treat local_hessian as single-rank for now.")
     if fp8_scale_sweep:
-        warnings.warn("local_hessian: fp8_scale_sweep=True searches static NVFP4 quantizers only (none on this path): "
-                      "every weight keeps its max-calibrated amax; pass fp8_scale_sweep=False for the multiplier search.")
-        accumulators.clear()
+        if not any(m.weight_quantizer.is_nvfp4_static for _, m in linears):
+            warnings.warn("local_hessian: fp8_scale_sweep=True searches static NVFP4 quantizers only (none in this "
+                          "model): every weight keeps its max-calibrated amax; pass fp8_scale_sweep=False for the "
+                          "multiplier search.")
+            accumulators.clear()
+            return
+        # the Hessian-weighted FP8 scale sweep of the static NVFP4 weights (a linear without samples or with cin % 16
+        # takes the plain sweep); every other weight stays at max
+        hess = {qid: (acc.normalized_hessian() if acc.is_enabled else None) for qid, acc in accumulators.items()}
+        _nvfp4_sweep_weights(model, hessian_for=lambda q: hess.get(id(q)))
+        if debug:
+            model._local_hessian_accumulators = accumulators
+        else:
+            accumulators.clear()
         return
     cout_of = {id(m.weight_quantizer): m.weight.shape[0] for _, m in linears}
     funcs = {qid: acc.build_error_func(cout_of[qid], keep_buffer=debug) for qid, acc in accumulators.items()}

@@ -80,6 +80,15 @@ MXINT8_DEFAULT_CFG = _mx_cfg(8)      # presets/model/mxint8.yaml
 # what runs here is its fake quantization and calibration (no packed export)
 _NVFP4_Q = {"num_bits": (2, 1), "axis": None, "block_sizes": {-1: 16, "type": "dynamic", "scale_bits": (4, 3)}}
 NVFP4_DEFAULT_CFG = _preset({"*weight_quantizer": dict(_NVFP4_Q), "*input_quantizer": dict(_NVFP4_Q)}, "max")
+# presets/model/nvfp4_w4a4_weight_{mse_fp8_sweep,local_hessian}.yaml: static NVFP4 weights (numerics/nvfp4_static.yaml:
+# per-16 block amax calibrated and kept, E4M3 block scales under a tensor-wide global amax) whose block scales come from the
+# FP8 scale sweep -- plain squared error, or weighted by the per-block input Hessian -- and dynamic NVFP4 inputs
+_NVFP4_STATIC_Q = {"num_bits": (2, 1), "block_sizes": {-1: 16, "type": "static", "scale_bits": (4, 3)}}
+NVFP4_W4A4_WEIGHT_MSE_FP8_SWEEP_CFG = _preset({"*weight_quantizer": dict(_NVFP4_STATIC_Q), "*input_quantizer": dict(_NVFP4_Q)},
+                                              {"method": "mse", "fp8_scale_sweep": True})
+NVFP4_W4A4_WEIGHT_LOCAL_HESSIAN_CFG = _preset({"*weight_quantizer": dict(_NVFP4_STATIC_Q),
+                                               "*input_quantizer": dict(_NVFP4_Q)},
+                                              {"method": "local_hessian", "fp8_scale_sweep": True})
 # presets/model/w4a8_awq_beta.yaml: INT4 blocks then FP8 on the weights, FP8 inputs; AWQ-lite searches on the INT4
 # stage with the input quantizers bypassed and max-calibrated per channel (model_calib.awq_lite)
 _W4A8_Q = {"*weight_quantizer": [{"num_bits": 4, "block_sizes": {-1: 128, "type": "static"}},

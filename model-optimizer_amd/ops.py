@@ -1344,3 +1344,80 @@ def block2d(x4: torch.Tensor, mode: int, amax: torch.Tensor | None = None, accum
     if mode == 0:
         return am
     return (y, am) if mode == 2 else y
+
+
+# ----------------------------------------------------------------------------------------------- static NVFP4 weights
+def _nvfp4_blocks(x: torch.Tensor, block_size: int, what: str):
+    """Flat [n_blocks, block_size] view of x (contiguous, 16-byte aligned) -- the reference's _prepare_block_sweep
+    contract (gemm/nvfp4_fp8_sweep.py:127-141)."""
+    _require_gpu(x, what)
+    _dt(x)
+    if not isinstance(block_size, int) or block_size <= 0:
+        raise ValueError(f"{what}: block_size must be a positive int, got {block_size!r}")
+    if block_size != 16:
+        raise MoquantUnsupported(f"{what}: NVFP4 blocks of 16 only (got {block_size})")
+    if x.numel() % block_size != 0:
+        raise ValueError(f"{what}: x.numel() ({x.numel()}) is not divisible by block_size ({block_size})")
+    xf = x.contiguous().view(-1)
+    if xf.data_ptr() % 16:
+        xf = xf.clone()
+    return xf, x.numel() // block_size
+
+
+def _global_amax(global_amax, device) -> torch.Tensor:
+    ga = _f32(torch.as_tensor(global_amax), device).reshape(-1)
+    if ga.numel() != 1:
+        raise MoquantUnsupported("NVFP4: global_amax must have one element")
+    return ga
+
+
+@torch.no_grad()
+def nvfp4_static_qdq(x: torch.Tensor, amax: torch.Tensor, global_amax: torch.Tensor, block_size: int = 16,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """static_blockwise_fp4_fake_quant(x, amax, global_amax, quantize_block_scales=True) (gemm/fp4_kernel.py:281-318):
+    E2M1 elements under FP8-E4M3 block scales fp8_eager(amax / 6, global_amax / 6).  Leading dims are flattened; the
+    output has x's shape and dtype."""
+    xf, n_blocks = _nvfp4_blocks(x, block_size, "nvfp4_static_qdq")
+    if amax.numel() != n_blocks:
+        raise ValueError(f"nvfp4_static_qdq: amax has {amax.numel()} elements for {n_blocks} blocks")
+    am = _f32(amax, x.device).view(-1)
+    ga = _global_amax(global_amax, x.device)
+    y = torch.empty_like(xf) if out is None else out.view(-1)
+    if y.dtype != xf.dtype or y.numel() != xf.numel() or not y.is_contiguous() or y.data_ptr() % 16:
+        raise MoquantUnsupported("nvfp4_static_qdq: out must be a contiguous, 16-byte aligned tensor like x")
+    with _on(xf) as stream:
+        check(_lib.lib().moq_nvfp4_static_qdq(_p(xf), _p(y), _p(am), _p(ga), n_blocks, 16, _dt(xf), stream))
+    return y.view(x.shape) if out is None else out
+
+
+@torch.no_grad()
+def nvfp4_fp8_scale_sweep(x: torch.Tensor, global_amax: torch.Tensor, block_size: int = 16) -> torch.Tensor:
+    """nvfp4_fp8_scale_sweep (gemm/nvfp4_fp8_sweep.py:144-180): per-block best_amax [n_blocks] fp32 over the 126 FP8
+    scale candidates, minimising the plain squared NVFP4 error."""
+    xf, n_blocks = _nvfp4_blocks(x, block_size, "nvfp4_fp8_scale_sweep")
+    ga = _global_amax(global_amax, x.device)
+    best = torch.empty(n_blocks, dtype=torch.float32, device=x.device)
+    with _on(xf) as stream:
+        check(_lib.lib().moq_nvfp4_fp8_sweep(_p(xf), _p(ga), _p(best), n_blocks, 16, _dt(xf), stream))
+    return best
+
+
+@torch.no_grad()
+def nvfp4_fp8_scale_sweep_hessian(x: torch.Tensor, global_amax: torch.Tensor, hessian: torch.Tensor,
+                                  block_size: int = 16) -> torch.Tensor:
+    """nvfp4_fp8_scale_sweep_hessian (gemm/nvfp4_fp8_sweep.py:229-290): the same search minimising dw^T H dw with the
+    per-cin-block Hessian `hessian` [cin // 16, 16, 16]; x is row-major over (cout, cin // 16) blocks."""
+    xf, n_blocks = _nvfp4_blocks(x, block_size, "nvfp4_fp8_scale_sweep_hessian")
+    if hessian.dim() != 3 or hessian.shape[1] != block_size or hessian.shape[2] != block_size:
+        raise ValueError(f"hessian must have shape [n_cin_blocks, {block_size}, {block_size}], got {tuple(hessian.shape)}")
+    ncb = hessian.shape[0]
+    if ncb == 0 or n_blocks % ncb != 0:
+        raise MoquantUnsupported(f"nvfp4_fp8_scale_sweep_hessian: n_blocks ({n_blocks}) is not divisible by "
+                                 f"n_cin_blocks ({ncb})")
+    h = _f32(hessian, x.device)
+    ga = _global_amax(global_amax, x.device)
+    best = torch.empty(n_blocks, dtype=torch.float32, device=x.device)
+    with _on(xf) as stream:
+        check(_lib.lib().moq_nvfp4_fp8_sweep_hessian(_p(xf), _p(h), _p(ga), _p(best), n_blocks, ncb, 16, _dt(xf),
+                                                     stream))
+    return best

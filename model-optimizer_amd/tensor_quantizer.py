@@ -262,6 +262,37 @@ class TensorQuantizer(nn.Module):
                 and self._fake_quant)
 
     @property
+    def is_nvfp4_static(self):
+        """E2M1 elements with static per-block E4M3 scales (tensor_quantizer.py: is_nvfp4_static): the block amax is
+        calibrated and kept, the FP8 block scales are taken relative to `global_amax`."""
+        nb, bs = self._num_bits, self._block_sizes
+        return (self.is_static_block_quant and not isinstance(nb, int) and tuple(nb) == (2, 1)
+                and tuple(bs.get("scale_bits") or ()) == (4, 3))
+
+    @property
+    def has_quantized_block_scale(self):
+        """The block scales themselves are quantized (to E4M3 under `global_amax`)."""
+        return self.is_nvfp4_static
+
+    @property
+    def global_amax(self):
+        """The tensor-wide amax of two-level block scaling (StaticBlockScaleQuantizer.global_amax, :1582-1600):
+        an fp32 scalar buffer `_global_amax`, None until set."""
+        return getattr(self, "_global_amax", None)
+
+    @global_amax.setter
+    def global_amax(self, value):
+        if value is None:
+            if "_global_amax" in self._buffers:
+                del self._buffers["_global_amax"]
+            return
+        value = torch.as_tensor(value).detach().to(dtype=torch.float32).reshape(())
+        if "_global_amax" in self._buffers:
+            self._global_amax.copy_(value.to(self._global_amax.device))
+        else:
+            self.register_buffer("_global_amax", value.clone())
+
+    @property
     def maxbound(self):
         if self._num_bits == (4, 3):
             return 448.0
@@ -296,8 +327,9 @@ class TensorQuantizer(nn.Module):
             self._amax = amax.to(dtype=torch.float32)
 
     def promote_static_block(self):
-        """StaticBlockScaleQuantizer.from_tensor_quantizer (tensor_quantizer.py:1521-1546) for INT static-block
-        weight quantizers: from now on the per-block amax is kept in fp32."""
+        """StaticBlockScaleQuantizer.from_tensor_quantizer (tensor_quantizer.py:1521-1546) for INT and static NVFP4
+        block weight quantizers: from now on the per-block amax is kept in fp32 (an NVFP4 one's `global_amax` is set by
+        the caller, model_calib.promote_static_block_weight_quantizers)."""
         self._is_static_block_scale_quantizer = True
         self._preserve_amax_in_fp32()
 
@@ -567,6 +599,9 @@ class TensorQuantizer(nn.Module):
             self.axis = (0,)
             return
         g = self._block_size_last(inputs)
+        if self.is_nvfp4_static and (g != 16 or inputs.shape[-1] % g):
+            raise MoquantUnsupported(f"static NVFP4: blocks of 16 along a last dim that 16 divides only "
+                                     f"(block {g}, last dim {inputs.shape[-1]})")
         self._original_shape = inputs.shape
         pad = (-inputs.shape[-1]) % g
         if pad:
@@ -653,6 +688,12 @@ class TensorQuantizer(nn.Module):
             # (tensor_quant.py:482) -- found by tools/quantizer_fuzz.py: a missing scale_bits used to mean E8M0 here
             assert isinstance(sb, (tuple, list)) and len(sb) == 2
             return ops.dynamic_block_quant(inputs, g, amax, nb, tuple(sb))
+        if self.is_nvfp4_static:
+            # StaticBlockScaleQuantizer._fake_quantize -> static_blockwise_fp4_fake_quant (tensor_quantizer.py:1721-1730);
+            # without a global amax compute_fp4_scales takes the max of the block amax (fp4_kernel.py:262-266)
+            amax = self._get_amax(inputs) if amax is None else amax
+            ga = self.global_amax
+            return ops.nvfp4_static_qdq(inputs, amax, amax.float().max() if ga is None else ga)
         if isinstance(self._num_bits, tuple):
             if tuple(self._num_bits) != (4, 3):
                 raise MoquantUnsupported(f"float format {self._num_bits} without dynamic blocks")

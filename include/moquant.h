@@ -542,6 +542,23 @@ int moq_nvfp4_fp8_sweep(const void* x, const float* global_amax, float* best_ama
  * best_amax[b] = fl(c_best * g).  n_blocks % n_cin_blocks != 0 (cin % 16 != 0) -> MOQ_ERR_UNSUPPORTED. */
 int moq_nvfp4_fp8_sweep_hessian(const void* x, const float* hessian, const float* global_amax, float* best_amax,
                                 int64_t n_blocks, int64_t n_cin_blocks, int block, int dt, void* stream);
+/* The checkpoint form -- NVFP4QTensor.quantize (qtensor/nvfp4_tensor.py:253-342) over n_blocks consecutive blocks of
+ * `block` (= 16) elements: 8 bytes of E2M1 nibbles (byte i = nibble[2i + 1] << 4 | nibble[2i]) and one E4M3 scale byte per block.
+ * All fp32, one rounding per operation.  With g = global_amax[0] and s2 = scale_2[0] (the caller's g / 2688, or any other
+ * per-tensor scale on the dynamic path):
+ *   amax != NULL (static blocks, get_weights_scaling_factor_from_quantizer):  s = amax[b] / 6, 1 where that is 0, then
+ *                 s = (s * 448) / (g / 6);
+ *   amax == NULL (dynamic blocks, get_weights_scaling_factor):  s = absmax(block) / (6 * s2), 1 where that is 0;
+ *   scale byte = e4m3_rne(clamp(s, 2^-9, 448)) (a NaN stays NaN);  q = x / (float(scale byte) * s2);
+ *   nibble = (q < 0) << 3 | code, code = q rounded half to even onto {0, .5, 1, 1.5, 2, 3, 4, 6}, saturating, 7 for a NaN.
+ * scales_given != 0: scale_e4m3 is read, not written (quantize with weights_scaling_factor); amax / global_amax unused.
+ * global_amax is read on the static path only.  x 16-byte, packed and amax 4-byte aligned. */
+int moq_nvfp4_pack(const void* x, const float* amax, const float* global_amax, const float* scale_2, uint8_t* packed,
+                   uint8_t* scale_e4m3, int scales_given, int64_t n_blocks, int block, int dt, void* stream);
+/* NVFP4QTensor.dequantize, the non-fast branch (:390-407): out = to_dt(e2m1_value[nibble] * (float(scale byte) * s2)), the
+ * value of nibble 8 being +0.  packed 4-byte, out 16-byte aligned. */
+int moq_nvfp4_unpack(const uint8_t* packed, const uint8_t* scale_e4m3, const float* scale_2, void* out, int64_t n_blocks,
+                     int block, int dt, void* stream);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,9 @@ SIGNATURES = {
     "moq_nvfp4_fp8_sweep": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "moq_nvfp4_fp8_sweep_hessian": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int,
                                             c_void_p]),
+    "moq_nvfp4_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
+                               c_void_p]),
+    "moq_nvfp4_unpack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
 }
 
 _lib = None

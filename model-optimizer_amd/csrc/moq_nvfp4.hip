@@ -2,6 +2,7 @@
 //   moq_nvfp4_static_qdq          static_blockwise_fp4_fake_quant (kernels/quantization/gemm/fp4_kernel.py:217-318)
 //   moq_nvfp4_fp8_sweep           _fp8_scale_sweep_kernel          (gemm/nvfp4_fp8_sweep.py:59-124)
 //   moq_nvfp4_fp8_sweep_hessian   _fp8_scale_sweep_hessian_kernel  (gemm/nvfp4_fp8_sweep.py:174-226)
+//   moq_nvfp4_pack / _unpack      NVFP4QTensor.quantize / .dequantize (qtensor/nvfp4_tensor.py:253-407), the checkpoint form
 //
 // The sweeps try the 126 positive finite E4M3 values c_k * 448 as block scales.  The reference rounds fl(|w| / s_k)
 // onto the E2M1 grid (fp4_round_magnitude, common/nvfp4_quant.py).  fl(a / s) is monotone in a, so each of the seven
@@ -9,7 +10,7 @@
 // the lower side.  The 126 x 7 boundaries and the 126 x 8 products fl(q * s) are computed (with IEEE divisions) once
 // per workgroup into LDS; an element-candidate then costs seven compares / selects, a subtraction and a square --
 // no division -- and gives the value of the correctly rounded quotient bit for bit.
-#include "moq_common.h"
+#include "moq_chunk.h"
 
 namespace moq {
 namespace {
@@ -233,6 +234,135 @@ __global__ void __launch_bounds__(kBlock) nvfp4_sweep_hessian_kernel(const void*
   }
 }
 
+// ------------------------------------------------------------------------------------------------ (d) pack / unpack
+// The stored byte of a block scale: torch's clamp(2^-9, 448) keeps a NaN, its cast to float8_e4m3fn is RNE.
+__device__ __forceinline__ uint32_t scale_byte(float s) {
+  if (s != s) return 0x7Fu | ((__float_as_uint(s) >> 24) & 0x80u);
+  const float c = __builtin_fminf(__builtin_fmaxf(s, 0x1p-9f), 448.0f);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, c, 0, false) & 0xFFu;
+}
+
+// NVFP4QTensor._cast_fp4 of one quotient: sign bit = (q < 0) (so -0 and NaN have none), magnitude code = round half to
+// even onto {0, .5, 1, 1.5, 2, 3, 4, 6}, saturating; a NaN gives 7.  a = min(|q|, 6) (a NaN becomes 6).  For a >= 1 the code
+// is the exponent field and the top mantissa bit of a rounded to nearest even at that bit (+4 folded into the rounding
+// constant, so that the low three bits are the code); below 1 the grid step is 0.5 and the fp32 addition of 2^22 -- whose
+// ulp is 0.5 -- rounds to it, ties to the even multiple, leaving the code in the low bits of the sum.
+__device__ __forceinline__ uint32_t e2m1_nibble(float q) {
+  const float a = __builtin_fminf(__builtin_fabsf(q), 6.0f);
+  const uint32_t u = __float_as_uint(a);
+  const uint32_t big = (u + 0x011FFFFFu + ((u >> 22) & 1u)) >> 22;
+  const uint32_t small = __float_as_uint(a + 0x1p22f);
+  return ((a < 1.0f ? small : big) & 7u) | (q < 0.0f ? 8u : 0u);
+}
+
+// One chunk of 8192 elements (512 blocks) per workgroup, one 16-byte packet per lane and step: a block is LPG = 2 lanes
+// (16-bit dtypes) or 4 (f32).  Every lane of a block forms the block's scale byte itself (the same operations on the same
+// values); the first one stores it.  The 16 quotients x / d of a block share d = fl(float(scale byte) * scale_2): inside
+// [2^-40, 2^20] and with every x of the packet zero or in [2^-100, 2^80] no quotient and no residual leaves the normal range
+// (an overflowing quotient would turn into a NaN in the residual steps and lose its sign), and the division is five FMAs on
+// a refined reciprocal, bit for bit the IEEE quotient (SharedDiv, moq_common.h); every other packet divides.
+// STATIC: block amax given.  GIVEN: the scale bytes are an input (NVFP4QTensor.quantize with weights_scaling_factor).
+template <int DT, bool STATIC, bool GIVEN>
+__global__ void __launch_bounds__(kBlock) nvfp4_pack_kernel(const void* __restrict__ x, const float* __restrict__ amax,
+                                                            const float* __restrict__ gamax,
+                                                            const float* __restrict__ scale2,
+                                                            uint8_t* __restrict__ packed, uint8_t* __restrict__ scales,
+                                                            int64_t n) {
+  constexpr int V = Elem<DT>::kVec;
+  constexpr int P = Chunk<DT>::kPackets;
+  constexpr int LPG = kNvBlock / V;
+  const float s2 = scale2[0];
+  const float six_s2 = 6.0f * s2;
+  float scale_max = 1.0f;
+  if constexpr (STATIC && !GIVEN) scale_max = gamax[0] / 6.0f;
+  const int64_t n_chunks = (n + MOQ_MT_CHUNK - 1) / MOQ_MT_CHUNK;
+  const int lane = threadIdx.x & 63;
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const int64_t e0 = c * MOQ_MT_CHUNK;
+    Pack16 in[P];
+    float am[P];
+    uint32_t sb[P];
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int64_t e = e0 + packet_off<DT>(u);
+      am[u] = 0.0f;
+      sb[u] = 0u;
+      if (e < n) {
+        in[u] = load16_nt(reinterpret_cast<const char*>(x) + e * (16 / V));
+        if constexpr (GIVEN) sb[u] = scales[e >> 4];
+        else if constexpr (STATIC) am[u] = amax[e >> 4];
+      } else {
+        in[u].w[0] = in[u].w[1] = in[u].w[2] = in[u].w[3] = 0u;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int64_t e = e0 + packet_off<DT>(u);
+      const uint32_t own_bits = pack_absmax<DT>(in[u]);
+      if constexpr (!GIVEN) {
+        float s;
+        if constexpr (STATIC) {
+          s = am[u] / 6.0f;
+          s = s == 0.0f ? 1.0f : s;
+          s = (s * 448.0f) / scale_max;
+        } else {
+          s = __uint_as_float(group_max_u32<LPG>(own_bits)) / six_s2;
+          s = s == 0.0f ? 1.0f : s;
+        }
+        sb[u] = scale_byte(s);
+      }
+      const float d = __builtin_amdgcn_cvt_f32_fp8((int)sb[u], 0) * s2;
+      const SharedDiv sd = make_shared_div(d);
+      const float ad = __builtin_fabsf(d);
+      const bool fast = ad >= 0x1p-40f && ad <= 0x1p20f && own_bits <= 0x67800000u /* 2^80 */ &&
+                        !pack_has_tiny_nonzero<DT>(in[u]);
+      float v[8];
+      unpack<DT>(in[u], v);
+      uint32_t word = 0;
+      if (fast) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) word |= e2m1_nibble(shared_div_in_window(v[i], sd)) << (4 * i);
+      } else {
+#pragma unroll
+        for (int i = 0; i < V; ++i) word |= e2m1_nibble(v[i] / d) << (4 * i);
+      }
+      if (e < n) {
+        if constexpr (V == 8) __builtin_nontemporal_store(word, reinterpret_cast<uint32_t*>(packed + e / 2));
+        else *reinterpret_cast<uint16_t*>(packed + e / 2) = (uint16_t)word;
+        if constexpr (!GIVEN) {
+          if ((lane & (LPG - 1)) == 0) scales[e >> 4] = (uint8_t)sb[u];
+        }
+      }
+    }
+  }
+}
+
+// 4 packed bytes -> 8 elements per lane: out = to_dt(e2m1_values[nibble] * fl(float(scale byte) * scale_2)); the table's
+// entry for nibble 8 is +0 (qtensor/nvfp4_tensor.py:27)
+template <int DT>
+__global__ void __launch_bounds__(kBlock) nvfp4_unpack_kernel(const uint8_t* __restrict__ packed,
+                                                              const uint8_t* __restrict__ scales,
+                                                              const float* __restrict__ scale2, void* __restrict__ out,
+                                                              int64_t n_words) {
+  constexpr int V = Elem<DT>::kVec;
+  const float s2 = scale2[0];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_words; p += stride) {
+    const uint32_t w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(packed) + p);
+    const float d = __builtin_amdgcn_cvt_f32_fp8((int)scales[p >> 1], 0) * s2;
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint32_t nib = (w >> (4 * i)) & 0xFu, m = nib & 7u;
+      const float mag = m < 2 ? 0.5f * (float)m : __uint_as_float(((m >> 1) + 126u) << 23 | (m & 1u) << 22);
+      v[i] = (m != 0 && (nib & 8u) ? -mag : mag) * d;
+    }
+#pragma unroll
+    for (int h = 0; h < 8 / V; ++h)
+      store16_nt(reinterpret_cast<char*>(out) + (p * 8 + h * V) * (16 / V), pack<DT>(v + h * V));
+  }
+}
+
 int launch_grid(int64_t items_per_wg_iter, int64_t items) { return stream_grid(items_per_wg_iter, items); }
 
 }  // namespace
@@ -311,4 +441,61 @@ extern "C" int moq_nvfp4_fp8_sweep_hessian(const void* x, const float* hessian, 
                        hessian, global_amax, best_amax, cout, n_cin_blocks);
   });
   return check_launch("moq_nvfp4_fp8_sweep_hessian");
+}
+
+extern "C" int moq_nvfp4_pack(const void* x, const float* amax, const float* global_amax, const float* scale_2,
+                              uint8_t* packed, uint8_t* scale_e4m3, int scales_given, int64_t n_blocks, int block, int dt,
+                              void* stream) {
+  const bool is_static = amax != nullptr;
+  if (n_blocks < 0 || (n_blocks > 0 && (!x || !scale_2 || !packed || !scale_e4m3 ||
+                                        (is_static && !scales_given && !global_amax)))) {
+    set_error("moq_nvfp4_pack: bad arguments");
+    return MOQ_ERR_INVALID;
+  }
+  if (block != kNvBlock) {
+    set_error("moq_nvfp4_pack: block size %d (only 16)", block);
+    return MOQ_ERR_UNSUPPORTED;
+  }
+  if (((uintptr_t)x & 15u) || ((uintptr_t)packed & 3u) || ((uintptr_t)amax & 3u)) {
+    set_error("moq_nvfp4_pack: x must be 16-byte, packed and amax 4-byte aligned");
+    return MOQ_ERR_UNSUPPORTED;
+  }
+  if (n_blocks == 0) return MOQ_OK;
+  const int64_t n = n_blocks * kNvBlock;
+  const int grid = copy_grid((n + MOQ_MT_CHUNK - 1) / MOQ_MT_CHUNK);
+  hipStream_t st = (hipStream_t)stream;
+#define MOQ_NVP_LAUNCH(S, G)                                                                                      \
+  MOQ_DISPATCH_DTYPE(dt, hipLaunchKernelGGL((nvfp4_pack_kernel<DT, S, G>), dim3(grid), dim3(kBlock), 0, st, x, amax, \
+                                            global_amax, scale_2, packed, scale_e4m3, n))
+  if (scales_given) {
+    MOQ_NVP_LAUNCH(false, true);
+  } else if (is_static) {
+    MOQ_NVP_LAUNCH(true, false);
+  } else {
+    MOQ_NVP_LAUNCH(false, false);
+  }
+#undef MOQ_NVP_LAUNCH
+  return check_launch("moq_nvfp4_pack");
+}
+
+extern "C" int moq_nvfp4_unpack(const uint8_t* packed, const uint8_t* scale_e4m3, const float* scale_2, void* out,
+                                int64_t n_blocks, int block, int dt, void* stream) {
+  if (n_blocks < 0 || (n_blocks > 0 && (!packed || !scale_e4m3 || !scale_2 || !out))) {
+    set_error("moq_nvfp4_unpack: bad arguments");
+    return MOQ_ERR_INVALID;
+  }
+  if (block != kNvBlock) {
+    set_error("moq_nvfp4_unpack: block size %d (only 16)", block);
+    return MOQ_ERR_UNSUPPORTED;
+  }
+  if (((uintptr_t)packed & 3u) || ((uintptr_t)out & 15u)) {
+    set_error("moq_nvfp4_unpack: packed must be 4-byte, out 16-byte aligned");
+    return MOQ_ERR_UNSUPPORTED;
+  }
+  if (n_blocks == 0) return MOQ_OK;
+  const int64_t words = n_blocks * 2;
+  hipStream_t st = (hipStream_t)stream;
+  MOQ_DISPATCH_DTYPE(dt, hipLaunchKernelGGL(nvfp4_unpack_kernel<DT>, dim3(launch_grid(kBlock, words)), dim3(kBlock), 0, st,
+                                            packed, scale_e4m3, scale_2, out, words));
+  return check_launch("moq_nvfp4_unpack");
 }

@@ -37,6 +37,9 @@ QUANTIZATION_W4A8_MXFP4_FP8 = "w4a8_mxfp4_fp8"
 QUANTIZATION_FP8_PB_WO = "fp8_pb_wo"
 QUANTIZATION_MXFP8 = "mxfp8"
 QUANTIZATION_FP8_PC_PT = "fp8_pc_pt"
+QUANTIZATION_NVFP4 = "nvfp4"
+QUANTIZATION_W4A16_NVFP4 = "w4a16_nvfp4"
+_NVFP4_FORMATS = (QUANTIZATION_NVFP4, QUANTIZATION_W4A16_NVFP4)
 
 
 def get_quantization_format(module) -> str | None:
@@ -79,6 +82,21 @@ def get_quantization_format(module) -> str | None:
         if (wq.block_sizes.get("type", "static") == "dynamic" and iq.is_enabled and inb == (4, 3) and iq.block_sizes is None):
             return QUANTIZATION_W4A8_MXFP4_FP8  # export/quant_utils.py:567-574: MXFP4 weights under per-tensor FP8 inputs
         return QUANTIZATION_MXFP4  # export/quant_utils.py:585-586
+    if (isinstance(nb, (tuple, list)) and tuple(nb) == (2, 1) and wq.block_sizes is not None
+            and tuple(wq.block_sizes.get("scale_bits") or ()) == (4, 3)):
+        # export/quant_utils.py:550-584, in its order: SVDQuant, AWQ (a smoothing scale, live or folded), weight-only, W4A4
+        if isinstance(module, _ExpertProjection):
+            raise NotImplementedError("export of fused experts with NVFP4 weight quantizers is outside this path")
+        if hasattr(wq, "svdquant_lora_a"):
+            raise NotImplementedError("export of NVFP4 SVDQuant weights (nvfp4_svdquant) is outside this path")
+        if getattr(iq, "_pre_quant_scale", None) is not None or getattr(module, "fused_with_prequant", False):
+            raise NotImplementedError("export of NVFP4-AWQ weights (nvfp4_awq) is outside this path")
+        if not wq.is_nvfp4_static:
+            raise NotImplementedError(f"export of dynamic NVFP4 blocks (num_bits={nb} block_sizes={wq.block_sizes}) is outside "
+                                      "this path: static NVFP4 weight quantizers only")
+        if wq.block_sizes.get("four_over_six", False):
+            raise NotImplementedError("export of four-over-six NVFP4 block scales is outside this path")
+        return QUANTIZATION_NVFP4 if iq.is_enabled else QUANTIZATION_W4A16_NVFP4
     raise NotImplementedError(f"export of weight format num_bits={nb} block_sizes={wq.block_sizes} is outside this path")
 
 
@@ -172,6 +190,12 @@ def preprocess_linear_fusion(modules, resmooth_only: bool = False):
             weight_amax = torch.max(torch.stack([m.weight_quantizer[-1].amax for m in modules]))
             for m in modules:
                 m.weight_quantizer[-1].amax = weight_amax
+    elif wq0.is_nvfp4_static:  # :1526-1536: fused at deployment under ONE per-tensor scale -- the largest global amax
+        global_amaxes = [m.weight_quantizer.global_amax for m in modules if m.weight_quantizer.global_amax is not None]
+        if global_amaxes:
+            unified = torch.max(torch.stack(global_amaxes))
+            for m in modules:
+                m.weight_quantizer.global_amax = unified
     elif wq0.is_enabled and wq0.amax is not None and wq0.amax.numel() == 1:
         weight_amax = torch.max(torch.stack([m.weight_quantizer.amax for m in modules]))
         for m in modules:
@@ -526,6 +550,19 @@ def export_quantized_weight(module, dtype: torch.dtype):
         if pqs is not None:  # SmoothQuant scaling composed with MXFP4: promoted like every other format's (:1121-1138)
             out["pre_quant_scale"] = pqs.detach().clone()
         return out
+    if fmt in _NVFP4_FORMATS:
+        # unified_export_hf.py:680-712, export/quant_utils.py:283-303, :913-933: block scales from the quantizer's block amax
+        # under its global amax, then NVFP4QTensor.quantize with both scales -- here one pass over the weight (moq_nvfp4_pack).
+        # These formats carry no smoothing scale (one on the input quantizer makes the format nvfp4_awq, refused above)
+        from .qtensor import NVFP4QTensor
+
+        if wq.global_amax is None or getattr(wq, "_amax", None) is None:
+            raise ValueError("NVFP4 export: the static weight quantizer has no calibrated block amax / global_amax")
+        qt, scale, scale_2 = NVFP4QTensor.quantize_from_quantizer(wq, module.weight.detach().to(dtype))
+        out = {"weight": qt._quantized_data, "weight_scale": scale, "weight_scale_2": scale_2.squeeze()}
+        if iq.is_enabled and iq.amax is not None:
+            out["input_scale"] = NVFP4QTensor.get_activation_scaling_factor(iq).squeeze()
+        return out
     if fmt == QUANTIZATION_MXFP8:
         # unified_export_hf.py:671-679, export/quant_utils.py:871-872: E8M0 scale bytes [Cout, Cin / 32] from the block
         # abs-max, E4M3 elements from the tile pack kernel
@@ -808,6 +845,8 @@ def _layer_quant_config(fmt: str, block: int) -> dict:
         return {"quant_algo": "W4A8_MXFP4_FP8", "group_size": block}
     if fmt == QUANTIZATION_MXFP8:
         return {"quant_algo": "MXFP8", "group_size": block}
+    if fmt in _NVFP4_FORMATS:  # (:726-735; the reference's per-layer key of a static quantizer is "nvfp4_static")
+        return {"quant_algo": "NVFP4" if fmt == QUANTIZATION_NVFP4 else "W4A16_NVFP4", "group_size": block}
     return {"quant_algo": _QUANT_ALGO.get(fmt, fmt)}  # (mxfp4, fp8_pb_wo: the format's own name)
 
 
@@ -885,6 +924,9 @@ def _group_of(algo: str, group_size: int | None) -> dict:
                                 {"dynamic": False, "num_bits": 8, "type": "int", "strategy": "channel"}, None),
         "W4A8_MXFP4_FP8": (dict(f8), {"dynamic": False, "num_bits": 4, "type": "float", "group_size": group_size or 16}, None),
         "MXFP8": (dict(f8, group_size=group_size or 32), dict(f8, group_size=group_size or 32), None),
+        "NVFP4": ({"dynamic": False, "num_bits": 4, "type": "float", "group_size": group_size or 16},
+                  {"dynamic": False, "num_bits": 4, "type": "float", "group_size": group_size or 16}, None),
+        "W4A16_NVFP4": (None, {"dynamic": False, "num_bits": 4, "type": "float", "group_size": group_size or 16}, None),
     }
     if algo not in table:
         warnings.warn(f"Unsupported quantization algorithm '{algo}' in the config-group table: the group carries the name only")
@@ -903,6 +945,8 @@ def convert_hf_quant_config_format(input_config: dict) -> dict:
     out: dict = {}
     if algo == "FP8":
         out["config_groups"] = {"group_0": {**_group_of("FP8", None), "targets": ["Linear"]}}
+    elif algo in ("NVFP4", "W4A16_NVFP4"):  # (:191-212)
+        out["config_groups"] = {"group_0": {**_group_of(algo, q.get("group_size", 16)), "targets": ["Linear"]}}
     elif algo == "MIXED_PRECISION":
         layers = q.get("quantized_layers", {})
         by_cfg = defaultdict(list)

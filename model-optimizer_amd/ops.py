@@ -1421,3 +1421,72 @@ def nvfp4_fp8_scale_sweep_hessian(x: torch.Tensor, global_amax: torch.Tensor, he
         check(_lib.lib().moq_nvfp4_fp8_sweep_hessian(_p(xf), _p(h), _p(ga), _p(best), n_blocks, ncb, 16, _dt(xf),
                                                      stream))
     return best
+
+
+# ----------------------------------------------------------------------------------------------- NVFP4 checkpoint form
+def _nvfp4_rows(x: torch.Tensor, block_size: int, what: str):
+    """_nvfp4_blocks for a tensor whose LAST dim is cut into blocks (a weight [..., cin]): cin % 16 is refused too."""
+    if isinstance(block_size, int) and block_size > 0 and x.dim() and x.shape[-1] % block_size:
+        _require_gpu(x, what)
+        raise MoquantUnsupported(f"{what}: the last dim ({x.shape[-1]}) is not divisible by the block size ({block_size})")
+    return _nvfp4_blocks(x, block_size, what)
+
+
+@torch.no_grad()
+def nvfp4_quantize(x: torch.Tensor, block_size: int = 16, amax: torch.Tensor | None = None,
+                   global_amax: torch.Tensor | None = None, scale: torch.Tensor | None = None,
+                   scale_2: torch.Tensor | None = None):
+    """NVFP4QTensor.quantize (qtensor/nvfp4_tensor.py:253-342) in one kernel: (packed uint8 [..., cin / 2], scale
+    float8_e4m3fn [..., cin / 16], scale_2 fp32 0-dim).
+    `amax` ([n_blocks] block amax) with `global_amax`: the static path (get_weights_scaling_factor_from_quantizer), scale_2 =
+    global_amax / 2688.  Neither: the dynamic path, the block amax is the block's own abs-max and scale_2 = abs-max(x) / 2688.
+    `scale_2` overrides the per-tensor scale; `scale` (float8_e4m3fn, one per block) is used as given instead of being
+    computed.  The divisions by Python numbers go through numerics.div_scalar."""
+    from . import numerics
+
+    xf, n_blocks = _nvfp4_rows(x, block_size, "nvfp4_quantize")
+    if (amax is None) != (global_amax is None):
+        raise ValueError("nvfp4_quantize: amax and global_amax come together (static blocks) or not at all (dynamic)")
+    am = ga = None
+    if amax is not None:
+        if amax.numel() != n_blocks:
+            raise ValueError(f"nvfp4_quantize: amax has {amax.numel()} elements for {n_blocks} blocks")
+        am = _f32(amax, x.device).view(-1)
+        ga = _global_amax(global_amax, x.device)
+    if scale_2 is None:
+        scale_2 = numerics.div_scalar(ga if ga is not None else reduce_amax(xf), 6.0 * 448.0)
+    s2 = _f32(torch.as_tensor(scale_2), x.device).reshape(-1)
+    if s2.numel() != 1:
+        raise MoquantUnsupported("nvfp4_quantize: scale_2 must have one element")
+    packed = torch.empty(*x.shape[:-1], x.shape[-1] // 2, dtype=torch.uint8, device=x.device)
+    if scale is not None:
+        if scale.dtype != torch.float8_e4m3fn or scale.numel() != n_blocks:
+            raise ValueError(f"nvfp4_quantize: scale must be float8_e4m3fn with one element per block ({n_blocks})")
+        sc = scale.detach().to(x.device).contiguous()
+    else:
+        sc = torch.empty(*x.shape[:-1], x.shape[-1] // 16, dtype=torch.float8_e4m3fn, device=x.device)
+    with _on(xf) as stream:
+        check(_lib.lib().moq_nvfp4_pack(_p(xf), _p(am), _p(ga), _p(s2), _p(packed), _p(sc), int(scale is not None), n_blocks,
+                                        16, _dt(xf), stream))
+    return packed, sc, s2.reshape(())
+
+
+@torch.no_grad()
+def nvfp4_dequantize(packed: torch.Tensor, scale: torch.Tensor, scale_2: torch.Tensor, dtype: torch.dtype,
+                     block_size: int = 16) -> torch.Tensor:
+    """NVFP4QTensor.dequantize, the non-fast branch (qtensor/nvfp4_tensor.py:390-407): [..., cin] of `dtype`."""
+    _require_gpu(packed, "nvfp4_dequantize")
+    if block_size != 16:
+        raise MoquantUnsupported(f"nvfp4_dequantize: NVFP4 blocks of 16 only (got {block_size})")
+    p = packed.detach().contiguous()
+    sc = scale.detach().to(p.device).contiguous()
+    if p.dtype != torch.uint8 or sc.dtype != torch.float8_e4m3fn or 2 * p.numel() != sc.numel() * 16:
+        raise MoquantError("nvfp4_dequantize: packed (uint8) / scale (float8_e4m3fn) type or size mismatch")
+    s2 = _f32(torch.as_tensor(scale_2), p.device).reshape(-1)
+    if s2.numel() != 1:
+        raise MoquantUnsupported("nvfp4_dequantize: scale_2 must have one element")
+    out = torch.empty(*p.shape[:-1], p.shape[-1] * 2, dtype=dtype, device=p.device)
+    _dt(out)
+    with _on(p) as stream:
+        check(_lib.lib().moq_nvfp4_unpack(_p(p), _p(sc), _p(s2), _p(out), sc.numel(), 16, _dt(out), stream))
+    return out

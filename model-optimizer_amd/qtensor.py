@@ -216,3 +216,127 @@ class MXFP8QTensor(BaseQuantizedTensor):
         out = ops.fp8_dequantize_tile(q.reshape(-1, k).view(torch.float8_e4m3fn), descale.reshape(-1, k // self.BLOCK_SIZE),
                                       torch.float32, 1, self.BLOCK_SIZE)
         return out.view(*q.shape)[..., : shape[-1]].to(dtype)
+
+
+class NVFP4QTensor(BaseQuantizedTensor):
+    """E2M1 elements in blocks of 16, one E4M3 scale per block, one fp32 scale per tensor (qtensor/nvfp4_tensor.py:49-407).
+
+    quantize and dequantize are one kernel each (`moq_nvfp4_pack`: scale bytes and nibbles in one pass, with the block amax
+    given -- static quantizers -- or taken from the block; `moq_nvfp4_unpack`).  The scalar `amax / (6 * 448)` runs where
+    numerics.mode() puts it; the committed fixtures pin "host", the reference's CPU run.  Not carried over, and refused
+    rather than ignored: `keep_high_precision`, `try_tensorrt`, the Triton `fast` dequantize and four-over-six block scales
+    (`fp8_max_for_normalization` = 256)."""
+
+    E2M1_MAX = 6.0
+    E4M3_MAX = 448.0
+    BLOCK_SIZE = 16
+
+    @staticmethod
+    def _refuse_four_over_six(quantizer) -> None:
+        bs = getattr(quantizer, "block_sizes", None) or {}
+        if bs.get("four_over_six", False):
+            raise MoquantUnsupported("NVFP4QTensor: four-over-six block scales (fp8_max_for_normalization = 256) are "
+                                     "outside this path")
+
+    @staticmethod
+    def _refuse(keep_high_precision=False, try_tensorrt=False, fast=False) -> None:
+        for flag, name in ((keep_high_precision, "keep_high_precision"), (try_tensorrt, "try_tensorrt"), (fast, "fast")):
+            if flag:
+                raise MoquantUnsupported(f"NVFP4QTensor: {name}=True is outside this path")
+
+    @classmethod
+    def _get_static_global_amax(cls, weight_quantizer):
+        g = getattr(weight_quantizer, "global_amax", None)
+        return g if g is not None else getattr(weight_quantizer, "_global_amax", None)
+
+    @classmethod
+    def _is_static_quantizer(cls, weight_quantizer) -> bool:
+        return cls._get_static_global_amax(weight_quantizer) is not None
+
+    @classmethod
+    def get_weights_scaling_factor_2_from_quantizer(cls, weight_quantizer) -> torch.Tensor:
+        """nvfp4_tensor.py:87-108: global_amax (static) or _amax (dynamic) / (6 * 448), fp32."""
+        cls._refuse_four_over_six(weight_quantizer)
+        g = cls._get_static_global_amax(weight_quantizer)
+        if g is None:
+            assert hasattr(weight_quantizer, "_amax"), "Weight quantizer does not have attribute amax"
+            g = weight_quantizer._amax
+        return numerics.div_scalar(g, cls.E2M1_MAX * cls.E4M3_MAX)
+
+    @classmethod
+    def get_weights_scaling_factor_2(cls, input: torch.Tensor) -> torch.Tensor:
+        """nvfp4_tensor.py:204-207."""
+        return numerics.div_scalar(ops.reduce_amax(input), cls.E2M1_MAX * cls.E4M3_MAX)
+
+    @classmethod
+    def get_weights_scaling_factor_from_quantizer(cls, weight_quantizer, weight: torch.Tensor,
+                                                  weights_scaling_factor_2: torch.Tensor | None = None,
+                                                  keep_high_precision: bool = False):
+        """nvfp4_tensor.py:110-166: (float8_e4m3fn [..., cin / 16], scale_2).  The scale bytes come out of the packer, so
+        this costs a pack whose nibbles are dropped; export_quantized_weight calls `quantize_from_quantizer` instead."""
+        cls._refuse(keep_high_precision=keep_high_precision)
+        _, scale, scale_2 = cls._pack_from_quantizer(weight_quantizer, weight, weights_scaling_factor_2)
+        return scale, scale_2
+
+    @classmethod
+    def _pack_from_quantizer(cls, weight_quantizer, weight, weights_scaling_factor_2=None):
+        cls._refuse_four_over_six(weight_quantizer)
+        block = weight_quantizer.block_sizes[-1]
+        if weights_scaling_factor_2 is None:
+            weights_scaling_factor_2 = cls.get_weights_scaling_factor_2_from_quantizer(weight_quantizer)
+        if cls._is_static_quantizer(weight_quantizer):
+            return ops.nvfp4_quantize(weight, block, amax=weight_quantizer._amax,
+                                      global_amax=cls._get_static_global_amax(weight_quantizer),
+                                      scale_2=weights_scaling_factor_2)
+        return ops.nvfp4_quantize(weight, block, scale_2=weights_scaling_factor_2)
+
+    @classmethod
+    def quantize_from_quantizer(cls, weight_quantizer, weight: torch.Tensor):
+        """get_weights_scaling_factor_from_quantizer followed by quantize with both scales (what the reference's exporter
+        does in two steps, export/quant_utils.py:300-303, :913-933), as ONE pass over the weight:
+        (NVFP4QTensor, scale, scale_2)."""
+        packed, scale, scale_2 = cls._pack_from_quantizer(weight_quantizer, weight)
+        return cls(weight.shape, weight.dtype, packed), scale, scale_2
+
+    @classmethod
+    def get_weights_scaling_factor(cls, input: torch.Tensor, block_size: int,
+                                   weights_scaling_factor_2: torch.Tensor | None = None, keep_high_precision: bool = False):
+        """nvfp4_tensor.py:168-202 (dynamic: the block amax is the block's abs-max)."""
+        cls._refuse(keep_high_precision=keep_high_precision)
+        assert block_size != 0, "Block size is zero. Cannot return per_block amax for given input."
+        _, scale, scale_2 = ops.nvfp4_quantize(input, block_size, scale_2=weights_scaling_factor_2)
+        return scale, scale_2
+
+    @classmethod
+    def get_activation_scaling_factor(cls, quantizer):
+        """nvfp4_tensor.py:209-227: amax.float() / (maxbound * 448)."""
+        if not quantizer.is_enabled:
+            return None
+        amax = quantizer.export_amax()
+        if amax is None:
+            return None
+        scale = numerics.div_scalar(amax, quantizer.maxbound * cls.E4M3_MAX)
+        assert torch.all(scale > 0), f" activation scaling factor {scale} not positive."
+        return scale
+
+    @classmethod
+    def quantize(cls, input: torch.Tensor, block_size: int, weights_scaling_factor: torch.Tensor | None = None,
+                 weights_scaling_factor_2: torch.Tensor | None = None, keep_high_precision: bool = False,
+                 try_tensorrt: bool = False):
+        """nvfp4_tensor.py:253-342: (NVFP4QTensor, scale, scale_2); a ragged last dim is zero-padded to a whole block."""
+        cls._refuse(keep_high_precision=keep_high_precision, try_tensorrt=try_tensorrt)
+        x = ops.reduce_block_padding(input, {-1: block_size}) if input.shape[-1] % block_size else input
+        packed, scale, scale_2 = ops.nvfp4_quantize(x, block_size, scale=weights_scaling_factor,
+                                                    scale_2=weights_scaling_factor_2)
+        return cls(input.shape, input.dtype, packed), scale, scale_2
+
+    def dequantize(self, dtype: torch.dtype = None, fast: bool = False, **kwarg):
+        """nvfp4_tensor.py:344-407, the non-fast branch: kwarg scale=, double_scale=, block_sizes=."""
+        self._refuse(fast=fast)
+        dtype = dtype or self.metadata["dtype"]
+        scale = kwarg["scale"]
+        if scale.dtype != torch.float8_e4m3fn:
+            raise MoquantUnsupported(f"NVFP4QTensor.dequantize: block scales must be float8_e4m3fn (got {scale.dtype})")
+        out = ops.nvfp4_dequantize(self._quantized_data, scale, kwarg["double_scale"], dtype, kwarg["block_sizes"][-1])
+        shape = self.metadata["shape"]
+        return out[..., : shape[-1]].reshape(shape)

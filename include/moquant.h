@@ -560,6 +560,24 @@ int moq_nvfp4_pack(const void* x, const float* amax, const float* global_amax, c
 int moq_nvfp4_unpack(const uint8_t* packed, const uint8_t* scale_e4m3, const float* scale_2, void* out, int64_t n_blocks,
                      int block, int dt, void* stream);
 
+/* ------------------------------------------------------------------ NVFP4 activation headroom calibration */
+
+/* The collect pass of NVFP4ActHeadroomCalibrator (calib/nvfp4_act_headroom.py:116-149) as ONE read of a contiguous
+ * [rows, cols] activation, cols % block == 0, block == 16 (other block sizes: MOQ_ERR_UNSUPPORTED).  For every block of 16
+ * along the last dim: a = max |x| in fp32;
+ *   a is NaN or Inf  ->  bad[0] |= 1 (NaN) or 2 (Inf), the block is not counted and does not reach running_max (the flag
+ *                        is per block abs-max: a block that holds both a NaN and an Inf reports NaN, which the
+ *                        reference asserts first);
+ *   a == 0           ->  dropped;
+ *   otherwise        ->  counts[#{k : thresholds[k] <= a}] += 1   and   running_max[0] = max(running_max[0], a).
+ * thresholds: `bins - 1` ascending positive fp32 values, compared as bit patterns -- the first value of every bin but the
+ * lowest, which the host bisects out of the reference's fp32 expression floor((log2(a) - lo) / (hi - lo) * bins) so that
+ * no logarithm is evaluated on the device; +Inf marks an edge no finite value reaches.  bins <= 4096.
+ * counts: 64-bit, exact, accumulated into the caller's buffer; running_max: fp32 >= 0, accumulated; bad: accumulated.
+ * x 16-byte, counts 8-byte, thresholds 4-byte aligned. */
+int moq_block_amax_log2_hist(const void* x, int64_t rows, int64_t cols, int dt, int block, const float* thresholds,
+                             int bins, unsigned long long* counts, float* running_max, int* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

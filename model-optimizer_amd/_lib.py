@@ -122,6 +122,8 @@ SIGNATURES = {
     "moq_nvfp4_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
                                c_void_p]),
     "moq_nvfp4_unpack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "moq_block_amax_log2_hist": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
 }
 
 _lib = None

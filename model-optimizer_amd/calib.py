@@ -12,9 +12,11 @@ Differences from the reference that do not change results:
 from __future__ import annotations
 
 import math
+import warnings
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import _lib, numerics, ops
 from ._lib import MoquantUnsupported
@@ -938,3 +940,158 @@ class NVFP4MSECalibrator(_Calibrator):
 
     def reset(self):
         self._best_amax = None
+
+
+_FP8_NORMAL_DYNAMIC_RANGE = 28672.0  # 448 / 2^-6: the ratio of block scales one global scale can hold as normal E4M3 values
+_ANCHOR_FLOOR_RATIO = 1e6            # block amaxes below upper / 1e6 are ignored when the anchor is located
+
+
+class NVFP4ActHeadroomCalibrator(_Calibrator):
+    """Global scale of a dynamic NVFP4 activation quantizer with headroom above the calibration data --
+    calib/nvfp4_act_headroom.py:36-230: amax = max(rho * anchor, upper), `anchor` and `upper` being the per-block (16) amax
+    at `anchor_percentile` and `upper_percentile` of a log2 histogram over all calibration batches.
+
+    State: `_hist` (int64 [num_bins]) and `_running_max` (0-dim fp32), as in the reference.
+
+    `collect` on a GPU tensor is ONE kernel (ops.block_amax_log2_hist): block abs-max, bin, running max and the NaN / Inf
+    test from one read of the batch, no temporaries; the bins are found by comparison with `ops.log2_hist_thresholds`, so
+    the counts are those of the reference's CPU run bit for bit.  Differences that do not change results:
+      * the reference asserts on NaN / Inf inside every `collect` (two device -> host syncs per batch, :129-134); here the
+        kernel raises a flag on the device, a poisoned block adds nothing to the counts or the running max, and the
+        reference's AssertionError is raised by `compute_amax` -- one host read per calibration;
+      * on the GPU `_hist` exists from the first collect on (whether a batch held a non-zero block is not asked of the
+        device); a histogram that stayed empty gives None like a missing one.
+    `collect` on a host tensor -- and with `use_kernel = False`, the checker of the GPU tests -- is the torch composition
+    of the same steps: block abs-max, log2, the bin expression, bincount.  Under numerics "host" its logarithm is taken on
+    the host for a device tensor too: torch's device log2 may differ from the host's in the last bit, next to a bin edge.
+    Numerics "device" (the reference's run on the tensors' own device) is that composition with the device's log2."""
+
+    use_kernel = True  # False: the torch composition on GPU tensors as well
+
+    def __init__(self, num_bits=(2, 1), axis=None, unsigned=False, *, block_size=16, anchor_percentile=1.0,
+                 upper_percentile=99.99, rho=16384.0, num_bins=512, log2_min=-40.0, log2_max=40.0):
+        super().__init__(num_bits, axis, unsigned)
+        if not (0.0 < rho < _FP8_NORMAL_DYNAMIC_RANGE):
+            raise ValueError(f"rho must be in (0, {_FP8_NORMAL_DYNAMIC_RANGE}); got {rho}. Larger rho gives "
+                             "more headroom above the calibrated range but less room below it.")
+        if not (0.0 < anchor_percentile <= 100.0):
+            raise ValueError(f"anchor_percentile must be in (0, 100]; got {anchor_percentile}.")
+        if not (0.0 < upper_percentile <= 100.0):
+            raise ValueError(f"upper_percentile must be in (0, 100]; got {upper_percentile}.")
+        self._block_size = block_size
+        self._anchor_percentile, self._upper_percentile, self._rho = float(anchor_percentile), float(upper_percentile), float(rho)
+        self._num_bins, self._log2_min, self._log2_max = int(num_bins), float(log2_min), float(log2_max)
+        self.reset()
+
+    def reset(self):
+        self._hist = None
+        self._running_max = None
+        self._bad = None  # int32 [1] on the device: bit 0 a NaN block, bit 1 an Inf block (kernel path)
+
+    def _bin_index(self, values: torch.Tensor) -> torch.Tensor:
+        return ops.log2_bin_index(values, self._num_bins, self._log2_min, self._log2_max)
+
+    @torch.no_grad()
+    def collect(self, x: torch.Tensor) -> None:
+        x = x.detach()
+        if self.use_kernel and numerics.on_host() and ops._is_gpu(x):
+            if self._bad is None:  # the first collect on a device; what the torch path gathered before moves there
+                dev = x.device
+                self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+                self._hist = (torch.zeros(self._num_bins, dtype=torch.int64, device=dev) if self._hist is None
+                              else self._hist.to(dev))
+                self._running_max = (torch.zeros((), dtype=torch.float32, device=dev) if self._running_max is None
+                                     else self._running_max.to(device=dev, dtype=torch.float32))
+            elif self._bad.device != x.device:
+                raise ValueError(f"NVFP4ActHeadroomCalibrator: statistics live on {self._bad.device}, this batch on "
+                                 f"{x.device}; reset() before calibrating on another device.")
+            table = ops.log2_hist_thresholds(self._num_bins, self._log2_min, self._log2_max, x.device)
+            ops.block_amax_log2_hist(x, self._block_size, table, self._hist, self._running_max, self._bad)
+            return
+        self._collect_torch(x)
+
+    def _collect_torch(self, x: torch.Tensor) -> None:
+        """The steps of the reference's collect (:116-149) as torch ops."""
+        bs = self._block_size
+        if x.shape[-1] % bs:
+            x = F.pad(x, (0, bs - x.shape[-1] % bs))
+        if x.is_cuda:
+            block_amax = ops.reduce_block_amax(x, {-1: bs})
+        else:
+            block_amax = x.reshape(*x.shape[:-1], x.shape[-1] // bs, bs).abs().amax(dim=-1)
+        block_amax = block_amax.flatten().float()
+        assert not torch.any(torch.isnan(block_amax)), \
+            f"detected nan values in amax. nan in original tensor: {torch.any(torch.isnan(x))}"
+        assert not torch.any(torch.isinf(block_amax)), \
+            f"detected inf values in amax. inf in original tensor: {torch.any(torch.isinf(x))}"
+        top = block_amax.max()
+        self._running_max = top if self._running_max is None else torch.maximum(self._running_max, top)
+        live = block_amax[block_amax > 0]
+        if live.numel() == 0:
+            return
+        if live.is_cuda and numerics.on_host():
+            live = live.cpu()  # the logarithm of the reference's CPU run
+        counts = torch.bincount(self._bin_index(live), minlength=self._num_bins)
+        if self._hist is None:
+            self._hist = torch.zeros(self._num_bins, dtype=torch.long, device=x.device)
+        self._hist += counts.to(self._hist.device)
+
+    @staticmethod
+    def _percentile_bin(counts: torch.Tensor, percentile: float):
+        total = counts.sum()
+        if total <= 0:
+            return None
+        cdf = torch.cumsum(counts, dim=0)
+        return int(torch.searchsorted(cdf, percentile / 100.0 * total).clamp(0, counts.numel() - 1).item())
+
+    def _percentile(self, hist: torch.Tensor, percentile: float, floor_value=None):
+        """Centre of the bin that holds `percentile` of the counts (:151-171); bins below `floor_value` do not count."""
+        counts = hist.float()
+        if floor_value is not None and floor_value > 0:
+            counts[:int(self._bin_index(torch.tensor(floor_value)).item())] = 0
+        b = self._percentile_bin(counts, percentile)
+        if b is None:
+            return None
+        return float(2.0 ** (self._log2_min + (b + 0.5) / self._num_bins * (self._log2_max - self._log2_min)))
+
+    @torch.no_grad()
+    def compute_amax(self):
+        """The calibrated global amax as a 0-dim fp32 tensor on the statistics' device, None when nothing was collected
+        (:173-218).  The arithmetic is the reference's host arithmetic on a host copy of the state (one read)."""
+        if self._hist is None or self._running_max is None:
+            return None
+        dev = self._running_max.device
+        if self._bad is not None:
+            state = torch.cat([self._hist, self._bad.to(torch.int64),
+                               self._running_max.reshape(1).view(torch.int32).to(torch.int64)]).cpu()
+            hist, bad = state[:-2], int(state[-2])
+            running_max = state[-1:].to(torch.int32).view(torch.float32).reshape(())
+            assert not bad & 1, "detected nan values in amax. nan in original tensor: True"
+            assert not bad & 2, "detected inf values in amax. inf in original tensor: True"
+            if int(hist.sum()) == 0:
+                return None  # every block of every batch was zero
+        else:
+            hist, running_max = self._hist.cpu(), self._running_max.cpu()
+        upper = float(running_max) if self._upper_percentile >= 100.0 else self._percentile(hist, self._upper_percentile)
+        anchor = self._percentile(hist, self._anchor_percentile, floor_value=upper / _ANCHOR_FLOOR_RATIO) if upper else None
+        if not upper or upper <= 0 or not anchor or anchor <= 0:
+            return running_max.clone().to(dev)  # the percentiles collapsed: plain max
+        headroom_amax = self._rho * anchor
+        if headroom_amax <= upper:
+            span = upper / anchor
+            if span > _FP8_NORMAL_DYNAMIC_RANGE:
+                advice = (f"The range also exceeds the FP8 scale range ({_FP8_NORMAL_DYNAMIC_RANGE:.0f}), so no permitted "
+                          "rho can clear it and no single global scale holds both ends. Reduce the range with outlier "
+                          "mitigation (SmoothQuant / per-channel / higher precision).")
+            else:
+                advice = "Lower anchor_percentile or raise rho for more headroom."
+            warnings.warn(f"[nvfp4_act_headroom] per-block amax range {span:.1f} leaves no headroom at rho={self._rho:g}; "
+                          f"the scale falls back to the top of the calibrated range. " + advice, stacklevel=2)
+            amax = upper
+        else:
+            amax = headroom_amax
+        return torch.tensor(float(amax), dtype=torch.float32, device=dev)
+
+    def __repr__(self):
+        return (f"NVFP4ActHeadroomCalibrator(anchor_percentile={self._anchor_percentile}, "
+                f"upper_percentile={self._upper_percentile}, rho={self._rho}, block_size={self._block_size})")

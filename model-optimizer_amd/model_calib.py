@@ -597,6 +597,72 @@ def local_hessian_calibrate(model: nn.Module, forward_loop=None, distributed_syn
         accumulators.clear()
 
 
+# ---------------------------------------------------------------------------------------- nvfp4_act_headroom
+def _is_nvfp4_dynamic_activation_quantizer(q) -> bool:
+    """An enabled NVFP4 quantizer with dynamic blocks (E2M1 under E4M3 block scales): its calibrated per-tensor `_amax` is the
+    global scale, the quantizer itself is not `_dynamic` (model_calib.py:501-517)."""
+    if not isinstance(q, TensorQuantizer) or q._disabled or q._dynamic:
+        return False
+    bs, nb = q.block_sizes, q.num_bits
+    return (bs is not None and bs.get("type", None) == "dynamic" and not isinstance(nb, int) and tuple(nb) == (2, 1)
+            and tuple(bs.get("scale_bits", None) or ()) == (4, 3))
+
+
+def _swap_in_nvfp4_act_headroom_calibrators(model: nn.Module, **options) -> list:
+    """(quantizer, its own calibrator) for every NVFP4 dynamic-block `*input_quantizer`, each now holding a fresh
+    calib.NVFP4ActHeadroomCalibrator (model_calib.py:529-564).  Refusals come first: a refused model is left as it was."""
+    from .calib import NVFP4ActHeadroomCalibrator
+
+    named = [(n, m) for n, m in model.named_modules() if n.endswith("input_quantizer")]
+    for n, m in named:
+        if isinstance(m, SequentialQuantizer) and any(_is_nvfp4_dynamic_activation_quantizer(q) for q in m.modules()):
+            raise NotImplementedError(
+                f"nvfp4_act_headroom does not support SequentialQuantizer activation quantizers, but {n!r} is one "
+                f"wrapping an NVFP4 dynamic-block quantizer. Use a single activation quantizer config for these modules, "
+                f"or calibrate with 'max'.")
+    fresh = [(m, NVFP4ActHeadroomCalibrator(m.num_bits, None, m._unsigned, block_size=m.block_sizes.get(-1, 16), **options))
+             for _, m in named if _is_nvfp4_dynamic_activation_quantizer(m)]  # (a bad option raises before any swap)
+    swapped = []
+    for q, cal in fresh:
+        swapped.append((q, q._calibrator))
+        q._calibrator = cal
+    return swapped
+
+
+@torch.no_grad()
+def nvfp4_act_headroom_calibrate(model: nn.Module, forward_loop=None, *, anchor_percentile: float = 1.0,
+                                 upper_percentile: float = 99.99, rho: float = 16384.0, weight_scale_algorithm=None):
+    """model_calib.nvfp4_act_headroom_calibrate (model_calib.py:567-636): the global scale of every NVFP4 dynamic-block
+    input quantizer from the distribution of its per-block amaxes, amax = max(rho * anchor, upper)
+    (calib.NVFP4ActHeadroomCalibrator), which leaves headroom above the calibration data where plain max leaves none.
+
+    The weights are a separate matter: `weight_scale_algorithm` is {"method": "max"} (the default, also for None), "mse"
+    or "local_hessian" with that algorithm's own options.  Each of them begins with max calibration, whose ONE forward
+    loop fills the swapped-in calibrators through the quantizers' plain `collect` (they are block quantizers with a
+    calibrator of their own class: neither the per-tensor fast path nor calib.DeferredAmax takes them); what follows
+    touches weights only.  The quantizers get their own calibrators back whatever happens.
+
+    Data parallel: every rank's amax comes from its own batches and the amaxes are MAX-reduced with all the others
+    (max_calibrate); the histograms are not pooled (the reference's note, :605-608)."""
+    algo = weight_scale_algorithm or {"method": "max"}
+    algo = {"method": algo} if isinstance(algo, str) else dict(algo)
+    method = algo.pop("method", None)
+    funcs = {"max": max_calibrate, "mse": mse_calibrate, "local_hessian": local_hessian_calibrate}
+    if method not in funcs:
+        raise ValueError(f"nvfp4_act_headroom: weight_scale_algorithm method {method!r} is not one of 'max', 'mse', "
+                         f"'local_hessian'")
+    swapped = _swap_in_nvfp4_act_headroom_calibrators(model, anchor_percentile=anchor_percentile,
+                                                      upper_percentile=upper_percentile, rho=rho)
+    if not swapped:
+        warnings.warn("nvfp4_act_headroom: no NVFP4 dynamic-block input quantizer matched, so this is equivalent to plain "
+                      "max calibration. Check that the recipe enables NVFP4 activation quantizers.")
+    try:
+        funcs[method](model, forward_loop, **algo)
+    finally:
+        for q, own in swapped:
+            q._calibrator = own
+
+
 # ------------------------------------------------------------------------------------------------ smoothquant
 @torch.no_grad()
 def apply_pre_quant_scale_and_smooth(linear: QuantLinear, pre_quant_scale: torch.Tensor, fold_later: list | None = None):

@@ -315,7 +315,7 @@ def quantize(model: nn.Module, config: dict, forward_loop=None) -> nn.Module:
 
 # algorithms that only write TensorQuantizer amax (QuantizeAlgorithmConfig._mutates_weights False, config.py:784-843):
 # the only ones whose layer-by-layer checkpoints may leave the weights out
-_AMAX_ONLY_ALGORITHMS = ("max", "mse", "local_hessian")
+_AMAX_ONLY_ALGORITHMS = ("max", "mse", "local_hessian", "nvfp4_act_headroom")
 
 
 def _layerwise_options(method, kwargs: dict) -> dict | None:
@@ -365,6 +365,12 @@ def _run_algorithm(model: nn.Module, algo, forward_loop):
         func = model_calib.mse_calibrate
     elif method == "local_hessian":
         func = model_calib.local_hessian_calibrate
+    elif method == "nvfp4_act_headroom":
+        # NVFP4ActHeadroomCalibConfig (config.py:1256-1328)
+        func = model_calib.nvfp4_act_headroom_calibrate
+        unknown = set(kwargs) - {"anchor_percentile", "upper_percentile", "rho", "weight_scale_algorithm"}
+        if unknown:
+            raise ValueError(f"unknown nvfp4_act_headroom option(s) {sorted(unknown)}")
     elif method == "smoothquant":
         func = model_calib.smoothquant
     elif method in ("awq_lite", "awq_clip", "awq_full"):
@@ -421,7 +427,7 @@ def _warn_invalid_quantizer_state(model: nn.Module):
 
 def calibrate(model: nn.Module, algorithm="max", forward_loop=None) -> nn.Module:
     """mtq.calibrate (quantization/model_quant.py:64-129): run a calibration algorithm on a model whose quantizers are in
-    place -- "max", "mse", "local_hessian", "smoothquant", "awq_lite" / "awq_clip" / "awq_full", "gptq", or a dict with
+    place -- "max", "mse", "local_hessian", "nvfp4_act_headroom", "smoothquant", "awq_lite" / "awq_clip" / "awq_full", "gptq", or a dict with
     "method" and the algorithm's keyword arguments; None does nothing.  A forward_loop that takes no argument is accepted
     with the reference's deprecation warning; the model is calibrated in eval mode and put back."""
     import inspect

@@ -1490,3 +1490,89 @@ def nvfp4_dequantize(packed: torch.Tensor, scale: torch.Tensor, scale_2: torch.T
     with _on(p) as stream:
         check(_lib.lib().moq_nvfp4_unpack(_p(p), _p(sc), _p(s2), _p(out), sc.numel(), 16, _dt(out), stream))
     return out
+
+
+# ----------------------------------------------------------------------------------------------- NVFP4 activation headroom
+def log2_bin_index(v: torch.Tensor, num_bins: int, log2_min: float, log2_max: float) -> torch.Tensor:
+    """Bin of every positive value of `v` in the log2 histogram of the headroom calibrator -- the reference's fp32
+    expression (calib/nvfp4_act_headroom.py:110-113, :145), on whatever device `v` lives."""
+    frac = (torch.log2(v) - log2_min) / (log2_max - log2_min)
+    return (frac * num_bins).floor().long().clamp_(0, num_bins - 1)
+
+
+_LOG2_HIST_TABLES: dict = {}
+
+
+def log2_hist_thresholds(num_bins: int, log2_min: float, log2_max: float, device=None) -> torch.Tensor:
+    """The `num_bins - 1` bin edges moq_block_amax_log2_hist compares against: entry k - 1 is the smallest positive fp32
+    value whose `log2_bin_index` ON THE HOST is >= k (+inf when no finite value reaches bin k).  The expression is monotone
+    in the value, so 31 bisection steps over the fp32 bit patterns, vectorised over the edges, find every edge exactly
+    (a few ms, once per (num_bins, log2_min, log2_max); cached per device).  With it the kernel reproduces the CPU run of
+    the reference bit for bit without evaluating a logarithm -- a device log2 one ulp off next to an edge would move a
+    block to the neighbouring bin."""
+    key = (int(num_bins), float(log2_min), float(log2_max))
+    host = _LOG2_HIST_TABLES.get((key, None))
+    if host is None:
+        k = torch.arange(1, key[0], dtype=torch.int64)
+        lo = torch.zeros_like(k)                       # pattern 0: below every edge
+        hi = torch.full_like(k, 0x7F800000)            # +inf: past every edge
+        for _ in range(31):
+            mid = (lo + hi) >> 1                       # a finite pattern; 0 only once an edge has come down to pattern 1
+            val = mid.clamp(min=1).to(torch.int32).view(torch.float32)
+            at = (mid > 0) & (log2_bin_index(val, *key) >= k)   # zero lies below every edge: no log2(0) is evaluated
+            hi = torch.where(at, mid, hi)
+            lo = torch.where(at, lo, mid)
+        host = hi.to(torch.int32).view(torch.float32).contiguous()
+        _LOG2_HIST_TABLES[(key, None)] = host
+    if device is None or torch.device(device).type == "cpu":
+        return host
+    dev = torch.device(device)
+    hit = _LOG2_HIST_TABLES.get((key, dev))
+    if hit is None:
+        hit = _LOG2_HIST_TABLES[(key, dev)] = host.to(dev)
+    return hit
+
+
+@torch.no_grad()
+def block_amax_log2_hist(x: torch.Tensor, block: int, thresholds: torch.Tensor, counts: torch.Tensor,
+                         running_max: torch.Tensor, bad: torch.Tensor) -> None:
+    """One read of an activation for NVFP4ActHeadroomCalibrator.collect (calib/nvfp4_act_headroom.py:116-149): per block
+    of `block` (= 16) along the last dim the abs-max; counts[bin] += 1 for every finite non-zero one, with
+    bin = #{k : thresholds[k] <= amax} (`log2_hist_thresholds`); running_max = max(running_max, amax); bad |= 1 / 2 when a
+    block amax is NaN / Inf (such a block is not counted).  A ragged last dim is zero-padded as the reference does
+    (:119-124) -- zeros change no block amax.  counts int64 [bins], thresholds fp32 [bins - 1], running_max fp32 and bad
+    int32 with one element each, all on x's device; they are updated in place.  `thresholds` must ascend (equal
+    neighbours allowed), as `log2_hist_thresholds` builds it: the kernel searches it by halving and an unsorted table
+    miscounts silently.  That is not checked here -- the table lives on the device and a check would cost every collect
+    a host sync."""
+    _require_gpu(x, "block_amax_log2_hist")
+    dt = _dt(x)
+    if not isinstance(block, int) or block <= 0:
+        raise ValueError(f"block_amax_log2_hist: block must be a positive int, got {block!r}")
+    if block != 16:
+        raise MoquantUnsupported(f"block_amax_log2_hist: NVFP4 blocks of 16 only (got {block})")
+    bins = counts.numel()
+    if counts.dtype != torch.int64 or not counts.is_contiguous() or bins < 1:
+        raise MoquantError("block_amax_log2_hist: counts must be a contiguous int64 tensor")
+    if thresholds.dtype != torch.float32 or not thresholds.is_contiguous() or thresholds.numel() != bins - 1:
+        raise MoquantError("block_amax_log2_hist: thresholds must be a contiguous fp32 tensor with one entry less than counts")
+    if running_max.dtype != torch.float32 or running_max.numel() != 1 or bad.dtype != torch.int32 or bad.numel() != 1:
+        raise MoquantError("block_amax_log2_hist: running_max must be one fp32 element and bad one int32 element")
+    for name, t in (("thresholds", thresholds), ("counts", counts), ("running_max", running_max), ("bad", bad)):
+        if t.device != x.device:
+            raise MoquantError(f"block_amax_log2_hist: {name} lives on {t.device}, x on {x.device}")
+    x = x.detach()
+    if x.dim() == 0:
+        x = x.reshape(1)
+    rem = x.shape[-1] % block
+    if rem:
+        x = F.pad(x, (0, block - rem))
+    x = x.contiguous()
+    if x.numel() == 0:
+        return
+    if x.data_ptr() % 16:
+        x = x.clone()
+    cols = x.shape[-1]
+    with _on(x) as stream:
+        check(_lib.lib().moq_block_amax_log2_hist(_p(x), x.numel() // cols, cols, dt, block, _p(thresholds), bins,
+                                                  _p(counts), _p(running_max), _p(bad), stream))

@@ -7,6 +7,7 @@ libmoquant.so (include/moquant.h).  Mirrors the reference's plugin surface for t
   calib            Max / Histogram / Mse calibrators with device-resident state
   tensor_quantizer TensorQuantizer (same attributes and life cycle as the reference's)
   nn, model_quant, model_calib   QuantLinear, quantize(), max_calibrate / smoothquant / awq_lite
+  awq_search       awq_lite: per-linear helper, Gram / error-GEMM scoring, tie check, layer-local walk (names re-exported by model_calib)
   hf_attention     q / k / v bmm quantizers (FP8 KV cache) on Hugging Face attention modules
   hf_experts       per-expert weight quantizers on fused 3-D MoE expert containers (Mixtral, Qwen-MoE, ...)
   sparsity         create_asp_mask (2:4 magnitude), SparseGPT
@@ -33,6 +34,7 @@ from . import hf_experts  # noqa: F401
 from . import hf_moe  # noqa: F401
 from . import distributed  # noqa: F401
 from . import model_calib  # noqa: F401
+from . import awq_search  # noqa: F401  (loaded by model_calib's last lines: model_calib must come first)
 from . import model_quant  # noqa: F401
 from . import sparsity  # noqa: F401
 from . import gptq  # noqa: F401

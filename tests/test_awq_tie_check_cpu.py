@@ -107,7 +107,7 @@ def test_a_requirement_above_the_margin_is_widened_until_the_exact_minimum_is_in
 
 
 def test_a_stricter_factor_widens_some_linears_of_this_model_and_changes_nothing(tables, monkeypatch):
-    monkeypatch.setattr(model_calib, "TIE_SPREAD_FACTOR", 2.0)
+    monkeypatch.setattr(moa.awq_search, "TIE_SPREAD_FACTOR", 2.0)  # (where tie_margin_check reads it)
     margin = model_calib.GRAM_TIE_MARGIN[moa.ops.torch.bfloat16] + model_calib.GRAM_PLANES_SLACK
     results = [_search(g, e, margin, check=True) for g, e in tables]
     assert all(w == _first_min(e) for (w, _, _), (_, e) in zip(results, tables))

@@ -319,7 +319,7 @@ def test_self_checking_margin_on_adversarial_distributions(kind, monkeypatch):
         assert [h.best_alpha for h in auto] == [h.best_alpha for h in gemm], f"{kind} seed {seed}"
         tc = st["tie_check"]
         assert tc["enabled"] and tc["max_need_over_margin"] <= 1.0 + 1e-9 or tc["widened_linears"] > 0
-    monkeypatch.setattr(model_calib, "TIE_SPREAD_FACTOR", 1e6)
+    monkeypatch.setattr(moa.awq_search, "TIE_SPREAD_FACTOR", 1e6)  # (where tie_margin_check reads it)
     gemm, _ = _run_adversarial(kind, 1, "gemm")
     forced, st = _run_adversarial(kind, 1, "auto", tie_margin=0.01)  # wide enough for near-ties on most linears
     assert [h.best_alpha for h in forced] == [h.best_alpha for h in gemm]

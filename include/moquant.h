@@ -578,6 +578,35 @@ int moq_nvfp4_unpack(const uint8_t* packed, const uint8_t* scale_e4m3, const flo
 int moq_block_amax_log2_hist(const void* x, int64_t rows, int64_t cols, int dt, int block, const float* thresholds,
                              int bins, unsigned long long* counts, float* running_max, int* bad, void* stream);
 
+/* ------------------------------------------------------------------ rotate: normalized Hadamard transform */
+
+/* y = scale * H_block * x per contiguous block of `block` elements of the last dim of a contiguous [rows, cols] tensor;
+ * block a power of two, 2 <= block <= 16384 (larger: MOQ_ERR_UNSUPPORTED), cols % block == 0.  H is the Sylvester
+ * (natural-order) Hadamard matrix.  The arithmetic is fixed: the block in fp32; for h = 1, 2, 4, ..., block / 2 in this
+ * order, for every i with (i & h) == 0, (v[i], v[i+h]) <- (v[i] + v[i+h], v[i] - v[i+h]), each one fp32 add; v[i] * scale
+ * with the caller's scale = float32(block ** -0.5); one RNE rounding to dt.  NaN / Inf propagate as the additions make
+ * them; nothing is flushed.  y may alias x.
+ * running_amax (optional, fp32[1]): running_amax[0] = max(running_amax[0], max |y|) over the ROUNDED outputs, with the NaN
+ * rule and the precondition of moq_amax's accumulate (the buffer holds a non-negative float or NaN) -- the rotation and
+ * MaxCalibrator.collect of the rotated tensor in one launch.
+ * Replaces normalized_hadamard_transform (quantization/nn/functional.py:81-138), which forwards to the CUDA-only package
+ * fast_hadamard_transform (hadamard_transform(x.reshape(-1, cols / block, block), scale = block ** -0.5)), as
+ * TensorQuantizer.forward calls it (nn/modules/tensor_quantizer.py:1142-1219).  Pointers that are not 16-byte aligned
+ * take a slow kernel with the same arithmetic. */
+int moq_hadamard(const void* x, void* y, int64_t rows, int64_t cols, int block, float scale, int dt,
+                 float* running_amax, void* stream);
+/* The rotation above with block = rot_block, then the dynamic block QDQ of moq_mx_fused_amax_convert (block, fmt, scale_fmt,
+ * global_amax as there) on the values ROUNDED to dt, then, if rotate_back != 0, the rotation again on the QDQ output (rounded
+ * to dt as well): bit for bit what moq_hadamard, moq_mx_fused_amax_convert and moq_hadamard write when launched in a row,
+ * in one read and one write.  This is TensorQuantizer.forward with rotate and a dynamic block format -- NVFP4 (E2M1
+ * elements, E4M3 scales, block 16) on the K states of NVFP4_KV_ROTATE_CFG (tensor_quantizer.py:1148-1150, :1207-1217;
+ * tensor_quant.py:157-195).  Fused for 16-byte aligned tensors, rot_block <= 512 (256 for f32), block dividing rot_block
+ * and in the fast layouts of moq_mx_fused_amax_convert (a power-of-two number of 16-byte lanes: at most 64 of them with
+ * E8M0 scales, 8 otherwise); everything else returns MOQ_ERR_UNSUPPORTED before any launch and the caller composes the
+ * three entries.  y may alias x. */
+int moq_hadamard_mx_qdq(const void* x, void* y, int64_t rows, int64_t cols, int rot_block, float scale, int block, int dt,
+                        int fmt, int scale_fmt, const float* global_amax, int rotate_back, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,9 @@ SIGNATURES = {
     "moq_nvfp4_unpack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "moq_block_amax_log2_hist": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
+    "moq_hadamard": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "moq_hadamard_mx_qdq": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

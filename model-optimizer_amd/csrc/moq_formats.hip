@@ -17,75 +17,6 @@ __device__ __forceinline__ bool al16(const void* p) {
 // Chunk skeleton: all packets of a chunk in flight before the first use, non-temporal loads and stores, dense
 // strided grid.  FMT >= 0 fixes the element format at compile time (E2M1 / E4M3: the MXFP4 / MXFP8 presets) so
 // that the rounding constants fold; FMT < 0 reads it from `fmt`.
-// block scale of the E8M0 formats / of the two-level (NVFP4-style) formats, as a functor of the block's abs-max
-struct MxScaleE8M0 {
-  float fmt_max;
-  __device__ __forceinline__ void operator()(float am, float& sc, float& un) const { mx_scale_e8m0(am, fmt_max, sc, un); }
-};
-struct MxScaleGeneral {
-  float fmt_max;
-  MxFmt sf;
-  const float* global;
-  __device__ __forceinline__ void operator()(float am, float& sc, float& un) const {
-    mx_scale_general(am, fmt_max, sf, global, sc, un);
-  }
-};
-// The two-level scales with a tensor-wide amax, without the two fp64 divisions per block of mx_scale_general (they, not
-// the memory stream, bounded the NVFP4-style kernel: 0.47 of 8 TB/s in round 4).  The block scale is
-//     q = (double)r / T,   r = round_to_scale_format(arg),   T = (double)sf.maxv * (double)(emax / global)   (one value per tensor)
-// and r is a scale-format value: r = M * 2^k with a 4-bit M in 8..15 whenever the scale format keeps at most three
-// mantissa bits (E4M3, E5M2, ...; k comes from r's fp32 exponent, subnormals of the scale format included).  Rounding
-// commutes with scaling by a power of two while nothing leaves the normal range, so
-//     unscale = (float)q       = (float)fl64(M / T)        * 2^k
-//     scale   = (float)(1 / q) = (float)fl64(1 / fl64(M / T)) * 2^-k
-// with the eight (M) pairs tabulated once per workgroup in LDS by the very fp64 divisions the reference performs.  A result
-// whose exponent would leave [-125, 126] (a block abs-max ~38 decades from the tensor's) takes mx_scale_general; r == 0
-// gives unscale 0 and scale +inf as there.
-struct MxScaleTwoLevelTable {
-  float fmt_max;
-  MxFmt sf;
-  const float* global;
-  double two_level;    // T
-  bool global_bad;
-  const float2* table;  // LDS: [M - 8] -> {(float)fl64(M / T), (float)fl64(1 / fl64(M / T))}
-  __device__ __forceinline__ void operator()(float am, float& sc, float& un) const {
-    sc = 1.0f;
-    un = 1.0f;
-    if (mx_bad_amax(am) || global_bad) return;
-    const float local_unscale = am / fmt_max;
-    const float arg = (float)((double)local_unscale * two_level);
-    const float r = mx_round_abs(arg, sf);
-    if (r == 0.0f) {
-      un = 0.0f;
-      sc = __uint_as_float(0x7F800000u);
-      return;
-    }
-    const uint32_t rb = __float_as_uint(r);
-    const int k = (int)((rb >> 23) & 0xFFu) - 130;  // r = (8 + top three mantissa bits) * 2^k
-    const float2 t = table[(rb >> 20) & 7u];
-    const int eu = (int)((__float_as_uint(t.x) >> 23) & 0xFFu) - 127 + k, es = (int)((__float_as_uint(t.y) >> 23) & 0xFFu) - 127 - k;
-    if (eu < -125 || eu > 126 || es < -125 || es > 126 || k < -126 || k > 126) {
-      mx_scale_general(am, fmt_max, sf, global, sc, un);
-      return;
-    }
-    un = t.x * __uint_as_float((uint32_t)(k + 127) << 23);
-    sc = t.y * __uint_as_float((uint32_t)(127 - k) << 23);
-  }
-};
-// the packet's block abs-max -> scale -> element rounding by integer ops: every format, every scale functor
-template <int DT, int LPG, class ScaleFn>
-__device__ __forceinline__ void mx_packet_general(float (&v)[8], const MxFmt f, const ScaleFn& scale_of) {
-  constexpr int V = Elem<DT>::kVec;
-  float am = 0.0f;
-#pragma unroll
-  for (int i = 0; i < V; ++i) am = __builtin_fmaxf(am, mx_abs_clamped(v[i]));
-  // non-negative floats order like their bit patterns
-  am = __uint_as_float(group_max_u32<LPG>(__float_as_uint(am)));
-  float sc, un;
-  scale_of(am, sc, un);
-#pragma unroll
-  for (int i = 0; i < V; ++i) v[i] = mx_qdq(v[i], sc, un, f);
-}
 // HW4: E2M1 elements with E8M0 scales (MXFP4) -- the chip's scaled FP4 converters (mx_e2m1_hw, moq_mx.h); a block they do
 // not take (a NaN inside, an exponent at the edge of the range) runs the general packet code: the branch is uniform over the
 // block's LPG lanes, so the DPP butterfly inside it sees whole blocks

@@ -618,7 +618,9 @@ def export_state_dict(model, dtype: torch.dtype, dummy_forward_fn=None, shard_we
     modules only (rank 0 also everything that is copied through), for `save_checkpoint` to write as this rank's
     safetensors shard.  The union over the ranks is the single-rank state dict, byte for byte."""
     from . import distributed as mdist
+    from .model_calib import refuse_rotation
 
+    refuse_rotation(model, "checkpoint export")  # (the packers read weights and amax, not the quantizer's forward)
     if dummy_forward_fn is not None:
         requantize_resmooth_fused_llm_layers(model, dummy_forward_fn)
     shard = mdist.resolve_shard(shard_weights)

@@ -303,6 +303,9 @@ def gptq(model: nn.Module, forward_loop, perc_damp: float = 0.01, block_size: in
     static NVFP4) has no meaning here: the elementwise formats are always one kernel per block.  `report_mse`: the
     Hessian-weighted relative error the reference prints per linear (two fp32 GEMMs against the Hessian each -- as much
     arithmetic as the update itself for wide linears) goes to GPTQ_STATS["relative_mse"]."""
+    from .model_calib import refuse_rotation
+
+    refuse_rotation(model, "gptq")
     from . import distributed as mdist
     from . import model_calib
     from .sparsity import _combine_hessians

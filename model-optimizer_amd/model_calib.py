@@ -117,6 +117,16 @@ def _foreign_weight_pairs(m) -> list:
     return [(w, q) for w, q in it() if isinstance(q, (TensorQuantizer, SequentialQuantizer))]
 
 
+def refuse_rotation(model: nn.Module, what: str):
+    """Raise for the first quantizer of `model` whose rotation is on: `what` (a calibration algorithm other than max, a
+    sparsity search, the checkpoint export) works on the tensors with kernels of its own, past TensorQuantizer.forward, and
+    would drop the rotation without a word."""
+    for name, mod in model.named_modules():
+        if isinstance(mod, TensorQuantizer) and mod.rotate_is_enabled:
+            raise MoquantUnsupported(f"{what} does not take rotating quantizers ({name}: rotate is enabled); only max "
+                                     "calibration, quantized forwards and fold_weight go through the rotation")
+
+
 def weight_only_quantize(model: nn.Module, shard: bool = False):
     """model_calib.py:187-199: pass every weight through its quantizer (collects weight statistics).
 
@@ -140,7 +150,8 @@ def weight_only_quantize(model: nn.Module, shard: bool = False):
     for w, wq in pairs:
         per_tensor_max = (isinstance(wq, TensorQuantizer) and wq._if_calib and wq.axis is None and wq.block_sizes is None
                           and type(wq._calibrator).__name__ == "MaxCalibrator" and w.is_cuda
-                          and w.is_contiguous() and wq.pre_quant_scale is None and wq.bias is None)
+                          and w.is_contiguous() and wq.pre_quant_scale is None and wq.bias is None
+                          and not wq.rotate_is_enabled)  # (the statistics are those of the ROTATED weight: its own forward)
         if per_tensor_max:
             batched.append((w, wq))
         else:
@@ -401,6 +412,7 @@ def mse_calibrate(model: nn.Module, forward_loop=None, distributed_sync: bool = 
                   shared_states=None):
     """model_calib.py:732-826 (multiplier search, fp8_scale_sweep=False): max calibration first, then every
     eligible weight quantizer's amax is refined by the MSE sweep -- here one fused kernel per weight."""
+    refuse_rotation(model, "mse_calibrate")
     if shared_states:
         # shared quantizer state other than the default sibling groups (model_calib.py:770-826) is outside this path
         raise MoquantUnsupported("mse_calibrate: shared_states are outside this path")
@@ -513,6 +525,7 @@ def local_hessian_calibrate(model: nn.Module, forward_loop=None, distributed_syn
     quantizers only -- every other quantizer is then left at its max-calibrated amax, as in the reference
     (_make_weight_mse_calibrator, :695-718); pass False for the multiplier search over the quantizers of this path.
     The Hessians are not combined across ranks (the reference warns the same)."""
+    refuse_rotation(model, "local_hessian_calibrate")
     if forward_loop is None:
         warnings.warn("forward_loop must be provided for local_hessian; skipping local_hessian")
         return
@@ -645,6 +658,7 @@ def nvfp4_act_headroom_calibrate(model: nn.Module, forward_loop=None, *, anchor_
 
     Data parallel: every rank's amax comes from its own batches and the amaxes are MAX-reduced with all the others
     (max_calibrate); the histograms are not pooled (the reference's note, :605-608)."""
+    refuse_rotation(model, "nvfp4_act_headroom_calibrate")
     algo = weight_scale_algorithm or {"method": "max"}
     algo = {"method": algo} if isinstance(algo, str) else dict(algo)
     method = algo.pop("method", None)
@@ -756,6 +770,7 @@ def smoothquant(model: nn.Module, forward_loop, alpha: float = 1.0, formats: str
               folded nor re-calibrated on the way: its smoothing fold rides INSIDE the MX quantize-dequantize, all such
               linears in ONE launch at one read + one write per element (multi_tensor.fold_mx_fused) instead of the fold's read
               + write, the re-calibration's read and the QDQ's read + write."""
+    refuse_rotation(model, "smoothquant")
     assert forward_loop is not None, "forward_loop must be provided for smoothquant"
     if formats not in ("int8", "all"):
         raise ValueError(f"smoothquant: formats must be 'int8' or 'all', got {formats!r}")
@@ -908,6 +923,7 @@ def awq_clip(model: nn.Module, forward_loop, max_co_batch_size: int = 1024, max_
     ratio of the block amax that minimises the block's output error on (sub-sampled) calibration tokens.
     `max_co_batch_size` bounds the reference's broadcast temporaries and has no effect here: the search is one
     kernel pass over the weight per forward call (ops.awq_clip_loss)."""
+    refuse_rotation(model, "awq_clip")
     assert forward_loop is not None, "forward_loop must be provided for awq_clip"
     mods = [(n, m) for n, m in model.named_modules()
             if is_quantized_linear(m) and m.weight_quantizer.is_enabled and m.weight_quantizer.block_sizes is not None]
@@ -966,6 +982,7 @@ def awq_clip(model: nn.Module, forward_loop, max_co_batch_size: int = 1024, max_
 @torch.no_grad()
 def awq(model: nn.Module, forward_loop=None, algorithm: str = "awq_lite", **kwargs):
     """model_calib.py:1362-1391: awq_lite, awq_clip or both (awq_full)."""
+    refuse_rotation(model, "awq")
     out = {}
     with SequentialQuantizer.convert_to_single_quantizer(model):  # search on the first (INT4) stage only (:1378)
         if algorithm in ("awq_full", "awq_lite"):

@@ -127,6 +127,20 @@ FP8_CAST_KV_CFG = {"quant_cfg": {"*[kv]_bmm_quantizer": {"num_bits": (4, 3), "ax
                    "algorithm": "max"}
 
 
+# presets/kv/nvfp4.yaml (units/kv_nvfp4.yaml) and presets/kv/nvfp4_rotate.yaml (units/kv_nvfp4_rotate.yaml), entry for entry
+# in the reference's list form: NVFP4 key / value quantizers; in the rotated preset the query and the key states are
+# rotated by the normalized Hadamard transform over the head dimension (the scores q . k are unchanged by a common
+# rotation), the query quantizer being there for its rotation only (disabled: it quantizes nothing).  The reference's
+# numerics unit also carries `effective_bits: 4.5`, the cost annotation of its auto_quantize search, which is no quantizer
+# attribute and has no reader here.
+_NVFP4_KV_Q = {"num_bits": (2, 1), "block_sizes": {-1: 16, "type": "dynamic", "scale_bits": (4, 3)}}
+NVFP4_KV_CFG = {"quant_cfg": [{"quantizer_name": "*[kv]_bmm_quantizer", "cfg": copy.deepcopy(_NVFP4_KV_Q)}]}
+NVFP4_KV_ROTATE_CFG = {"quant_cfg": [{"quantizer_name": "*q_bmm_quantizer", "cfg": {"rotate": True}, "enable": False},
+                                     {"quantizer_name": "*k_bmm_quantizer", "cfg": {**copy.deepcopy(_NVFP4_KV_Q), "rotate": True}},
+                                     {"quantizer_name": "*v_bmm_quantizer", "cfg": copy.deepcopy(_NVFP4_KV_Q)}],
+                       "algorithm": "max"}
+
+
 def update_quant_cfg_with_kv_cache_quant(quant_cfg: dict, kv_cache_quant_cfg: dict) -> dict:
     """utils/core_utils.py:1049-1075: a copy of `quant_cfg` with the KV-cache entries appended (later entries win);
     a config without an algorithm gets "max" so that the KV quantizers are calibrated."""
@@ -350,6 +364,10 @@ def _run_algorithm(model: nn.Module, algo, forward_loop):
     method, kwargs = (algo, {}) if not isinstance(algo, dict) else (algo["method"], {k: v for k, v in algo.items() if k != "method"})
     if method is None:
         return model
+    if method != "max":
+        # every other algorithm reaches the tensors through fused kernels of its own, past TensorQuantizer.forward, where
+        # the rotation lives: refused, never dropped
+        model_calib.refuse_rotation(model, f"algorithm {method!r}")
     lw = _layerwise_options(method, kwargs)
     ratio = kwargs.pop("moe_calib_experts_ratio", None)  # QuantizeAlgorithmConfig.moe_calib_experts_ratio (config.py:791-806)
     if ratio is not None:
@@ -579,7 +597,7 @@ class set_quantizer_by_cfg_context:
     turn a quantizer into a chain are refused there, and here."""
 
     _SAVED = ("_disabled", "_num_bits", "_axis", "_block_sizes", "_dynamic", "_unsigned", "_narrow_range", "_bias",
-              "_use_constant_amax", "_constant_amax", "_if_quant", "_if_calib")
+              "_use_constant_amax", "_constant_amax", "_rotate", "_if_quant", "_if_calib")
 
     def __init__(self, quant_model: nn.Module, quant_cfg):
         self.model, self.cfg = quant_model, quant_cfg
@@ -638,8 +656,8 @@ def _fold_kind(w, wq):
     import torch
 
     if (not w.is_cuda or not w.is_contiguous() or w.dtype not in (torch.float32, torch.float16, torch.bfloat16)
-            or wq.pre_quant_scale is not None or w.data_ptr() % 16 or w.numel() == 0):
-        return None
+            or wq.pre_quant_scale is not None or wq.rotate_is_enabled or w.data_ptr() % 16 or w.numel() == 0):
+        return None  # (a rotating quantizer is folded through its forward, quant_module.py:147-150)
     nb = wq._num_bits if not isinstance(wq._num_bits, list) else tuple(wq._num_bits)
     amax = getattr(wq, "_amax", None)
     if wq._block_sizes is None and wq._axis is None and amax is not None and amax.numel() == 1:
@@ -703,8 +721,8 @@ def fold_weight(model: nn.Module, keep_attrs: bool = False, shard_weights: bool 
     with torch.no_grad():
         groups, single = {}, []
         for w, wq in mine:
-            if wq._disabled and wq.pre_quant_scale is None:
-                continue  # disabled and no pre-quant scale on this path: the forward is the identity
+            if wq._disabled and wq.pre_quant_scale is None and not wq.rotate_is_enabled:
+                continue  # disabled, no pre-quant scale and no rotation on this path: the forward is the identity
             # (a disabled quantizer that still carries an active pre-quant scale IS folded -- its forward multiplies by
             # the scale before the disabled early return, quant_module.py:144-158 and its docstring :163-165)
             kind = _fold_kind(w, wq)
@@ -735,6 +753,7 @@ def fold_weight(model: nn.Module, keep_attrs: bool = False, shard_weights: bool 
                 continue
             seen.add(id(wq))
             wq.disable()
+            wq.disable_rotate()  # baked into the weight (quant_module.py:150)
             if keep_attrs and hasattr(wq, "_pre_quant_scale"):
                 wq._enable_pre_quant_scale = False
             elif not keep_attrs:

@@ -423,6 +423,95 @@ def dynamic_block_quant(inputs, block_size, amax, num_bits, scale_bits):
                               None if scale_bits == (8, 0) else amax)
 
 
+# ----------------------------------------------------------------------------------------------- rotate (Hadamard)
+HADAMARD_MAX_BLOCK = 16384
+
+
+def hadamard_block_size(dim: int, block_size: int | None = None) -> int:
+    """The block the rotation of a last dimension `dim` uses -- normalized_hadamard_transform's choice and errors
+    (nn/functional.py:108-130): None = the whole dimension when it is a power of two, else its largest power-of-two divisor."""
+    dim = int(dim)
+    if block_size is None:
+        block_size = dim & (-dim)
+        if block_size < 2:
+            raise RuntimeError(
+                f"Block RHT: dimension {dim} has no power-of-2 divisor >= 2. "
+                "Set rotate.block_size explicitly (e.g. 128) or use a dimension divisible by a power of 2.")
+    if isinstance(block_size, bool) or not isinstance(block_size, int) or block_size < 1 or block_size & (block_size - 1):
+        raise ValueError(f"Block RHT: block_size must be power of 2, got {block_size}.")
+    if dim % block_size != 0:
+        raise RuntimeError(
+            f"Block RHT: inputs.shape[-1]={dim} is not divisible by block_size={block_size}. "
+            f"Use a block_size that divides {dim} (e.g. {dim & (-dim)}).")
+    if block_size < 2:
+        raise MoquantUnsupported("hadamard: a rotation block of one element is not a rotation (block_size >= 2)")
+    if block_size > HADAMARD_MAX_BLOCK:
+        raise MoquantUnsupported(f"hadamard: rotation blocks above {HADAMARD_MAX_BLOCK} are not supported, got {block_size}")
+    return block_size
+
+
+def _hadamard_scale(block: int) -> float:
+    """float32(block ** -0.5): the value the kernel multiplies by (exact for even powers of two only)."""
+    return float(torch.tensor(block ** -0.5, dtype=torch.float32))
+
+
+@torch.no_grad()
+def hadamard(x: torch.Tensor, block_size: int | None = None, running_amax: torch.Tensor | None = None,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """Normalized Hadamard transform over blocks of the last dim -- normalized_hadamard_transform (nn/functional.py:81-138),
+    whose CUDA-only backend does not exist on ROCm.  The arithmetic is always fp32 and the result is rounded once to the
+    input dtype, so the reference's rotate_fp32 changes nothing here.  `running_amax` (fp32, one element) receives
+    max(running_amax, max |result|) in the same launch; `out` may be `x` (in place)."""
+    _require_gpu(x, "hadamard")
+    block = hadamard_block_size(x.shape[-1] if x.dim() else 1, block_size)
+    if running_amax is not None and (running_amax.dtype != torch.float32 or running_amax.numel() != 1
+                                     or running_amax.device != x.device):
+        raise MoquantError("hadamard: running_amax must be one fp32 element on the tensor's device")
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous()):
+        raise MoquantError("hadamard: out must be contiguous with the shape and dtype of the input")
+    src = x.detach().contiguous()  # (a strided view is copied first, so a contiguous `out` over the same memory is safe)
+    y = torch.empty_like(src) if out is None else out
+    cols = src.shape[-1]
+    with _on(src) as stream:
+        check(_lib.lib().moq_hadamard(_p(src), _p(y), src.numel() // max(cols, 1), cols, block, _hadamard_scale(block),
+                                      _dt(src), _p(running_amax), stream))
+    return y
+
+
+_HADAMARD_QDQ_FUSED = True  # False: always the standalone launches (tests and tools/hadamard_bench.py compare the two)
+
+
+@torch.no_grad()
+def hadamard_block_quant(x: torch.Tensor, rot_block: int | None, block_size: int, amax, num_bits, scale_bits,
+                         rotate_back: bool = False) -> torch.Tensor:
+    """hadamard -> dynamic_block_quant -> (rotate_back) hadamard as ONE launch where moq_hadamard_mx_qdq has a kernel, and
+    as those launches in a row -- the same bits -- where it answers MOQ_ERR_UNSUPPORTED.  TensorQuantizer.forward with
+    rotate and a dynamic block format (tensor_quantizer.py:1148-1150, :1207-1217)."""
+    _require_gpu(x, "hadamard_block_quant")
+    if num_bits not in _MX_FORMAT_MAP or scale_bits not in _MX_FORMAT_MAP:
+        raise NotImplementedError(f"Unsupported num_bits: {num_bits}, scale_bits: {scale_bits}")
+    rot = hadamard_block_size(x.shape[-1] if x.dim() else 1, rot_block)
+    src = x.detach().contiguous()
+    f, sf = _lib.MX_TYPES[_MX_FORMAT_MAP[num_bits]], _lib.MX_TYPES[_MX_FORMAT_MAP[scale_bits]]
+    ga = None if scale_bits == (8, 0) or amax is None else _f32(amax, src.device)
+    if ga is not None and ga.numel() != 1:
+        raise MoquantUnsupported("hadamard_block_quant: global_amax must have one element")
+    y = torch.empty_like(src)
+    if _HADAMARD_QDQ_FUSED:
+        cols = src.shape[-1]
+        try:
+            with _on(src) as stream:
+                check(_lib.lib().moq_hadamard_mx_qdq(_p(src), _p(y), src.numel() // max(cols, 1), cols, rot,
+                                                     _hadamard_scale(rot), int(block_size), _dt(src), f, sf, _p(ga),
+                                                     int(bool(rotate_back)), stream))
+            return y
+        except MoquantUnsupported:
+            pass  # no fused kernel for this layout: the standalone launches, which also name a bad format themselves
+    hadamard(src, rot, out=y)
+    fused_amax_convert(y, block_size, f, sf, ga, out=y)
+    return hadamard(y, rot, out=y) if rotate_back else y
+
+
 # ----------------------------------------------------------------------------------------------- histogram
 @torch.no_grad()
 def hist_abs(x: torch.Tensor, bins: int, max_edge: float, skip_zeros: bool = False,

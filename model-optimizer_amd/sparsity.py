@@ -255,7 +255,9 @@ def sparsify(model: torch.nn.Module, mode: str = "sparse_magnitude", forward_loo
     (sample-weighted SUM, the running mean of sparsegpt.py:238-276 over ALL batches), and only the owner inverts the
     Hessian and sweeps the linears that read it."""
     from . import distributed as mdist
+    from .model_calib import refuse_rotation
 
+    refuse_rotation(model, f"sparsify({mode!r})")  # (the mask searches read the weights, not a quantizer's forward)
     cfg = {"pattern": _PATTERN_2_4, "col_block_size": 128, "row_block_size": -1, "hessian_damp": 0.1, **(config or {})}
     shard = mdist.resolve_shard(shard_weights)
     applied: set = set()

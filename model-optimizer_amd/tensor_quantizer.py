@@ -9,14 +9,15 @@ search inner loop), and otherwise one kernel per stage.  GPU tensors only: there
 
 Scope: fake quantization for INT-k (per-tensor / per-channel / static last-axis blocks), FP8-E4M3
 (per-tensor / per-channel), dynamic MX blocks, static block grids on any axes (last axis and last-two-axes tiles without a copy), and the affine
-offset (`bias`) of the KV-cache presets.  Rotation and real-quant QTensors are outside this path and raise.
+offset (`bias`) of the KV-cache presets, and rotation (a normalized Hadamard transform of the last dim before the
+quantizer, optionally again after it).  Real-quant QTensors are outside this path and raise.
 """
 
 from __future__ import annotations
 
 import math
 import warnings
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import torch
 import torch.distributed as dist
@@ -26,6 +27,42 @@ from torch import nn
 from . import ops
 from ._lib import MoquantUnsupported
 from .calib import BiasCalibrator, HistogramCalibrator, MaxCalibrator, _Calibrator, convert_quantization_axis_to_reduce_axis
+
+
+@dataclass(frozen=True)
+class RotateConfig:
+    """config.py:282-320: rotate the quantizer's input by a normalized Hadamard transform over blocks of the last dim
+    (ops.hadamard).  mode "rotate_back" applies the transform again after the fake quantization.  rotate_fp32 is accepted
+    and changes nothing: the kernels always compute in fp32 and round once to the input dtype, which is also what the
+    reference's rotate_fp32 path returns (`outputs.to(dtype)`, nn/functional.py:138)."""
+
+    enable: bool = False
+    mode: str = "rotate"
+    rotate_fp32: bool = False
+    block_size: int | None = None
+
+    def __post_init__(self):
+        if not isinstance(self.enable, bool) or not isinstance(self.rotate_fp32, bool):
+            raise ValueError("rotate.enable and rotate.rotate_fp32 must be bool")
+        if self.mode not in ("rotate", "rotate_back"):
+            raise ValueError(f"rotate.mode must be 'rotate' or 'rotate_back', got {self.mode!r}")
+        v = self.block_size
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v <= 0):
+            raise ValueError(f"block_size must be a positive int, got {v!r}")  # (config.py:313-319)
+
+    @classmethod
+    def of(cls, v) -> "RotateConfig":
+        """A bool is `enable` with everything else at its default (config.py:616-625); a dict names the fields."""
+        if isinstance(v, cls):
+            return v
+        if isinstance(v, bool):
+            return cls(enable=v)
+        if isinstance(v, dict):
+            unknown = set(v) - {"enable", "mode", "rotate_fp32", "block_size"}
+            if unknown:
+                raise ValueError(f"unknown rotate option(s) {sorted(unknown)}")
+            return cls(**v)
+        raise ValueError(f"rotate must be a bool or a dict, got {v!r}")
 
 
 @dataclass
@@ -48,9 +85,11 @@ class QuantizerAttributeConfig:
     # `_amax` buffer (the cast-style KV-cache presets); constant_amax = `_amax` pinned to the value, forward and export
     use_constant_amax: bool = False
     constant_amax: float | None = None
+    rotate: bool | dict | RotateConfig = False  # normalised to a RotateConfig (config.py:616-625)
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
+        self.rotate = RotateConfig.of(self.rotate)
         assert self.constant_amax is None or self.constant_amax > 0, "constant_amax must be a positive value."
         assert not (self.use_constant_amax and self.constant_amax is not None), \
             "use_constant_amax and constant_amax are mutually exclusive; set only one."
@@ -141,12 +180,14 @@ class TensorQuantizer(nn.Module):
                  _unsigned=cfg.unsigned, _narrow_range=cfg.narrow_range, _fake_quant=cfg.fake_quant, _disabled=not cfg.enable,
                  _dynamic=cfg.type == "dynamic", _bias=dict(cfg.bias) if cfg.bias else None,
                  _bias_calibrator=None,  # made on first use (tensor_quantizer.py:222-223, :490-503)
-                 _use_constant_amax=bool(cfg.use_constant_amax), _constant_amax=cfg.constant_amax)
+                 _use_constant_amax=bool(cfg.use_constant_amax), _constant_amax=cfg.constant_amax,
+                 _rotate=RotateConfig.of(cfg.rotate))
         d["_calibrator"] = self._make_calibrator(cfg.calibrator)
         if cfg.constant_amax is not None:  # pinned on the buffer: forward and export read it (tensor_quantizer.py:256-261)
             self.amax = float(cfg.constant_amax)
 
     # ------------------------------------------------------------------ configuration
+    _rotate = RotateConfig()   # (instances made before the attribute existed, e.g. unpickled ones: no rotation)
     _weight_stats_done = None  # (data_ptr, version, shape) of the weight whose max statistics this calibration already holds
 
     _LAYOUT_CACHES = ("_block_reshape_size", "_padding", "_slices", "_original_shape", "_amax_shape_for_export", "_block_amax_view",
@@ -177,7 +218,10 @@ class TensorQuantizer(nn.Module):
         block sizes clear the axis, a constant amax is pinned on the buffer -- and everything else, calibration state included,
         stays as it is."""
         for key in partial:
-            if key in ("rotate", "backend", "backend_extra_args", "learn_amax", "trt_high_precision_dtype", "pass_through_bwd"):
+            if key == "rotate":
+                raise MoquantUnsupported("quantizer attribute 'rotate' is not taken by a partial update: set it with the full "
+                                         "configuration (set_from_attribute_config / set_quantizer_attributes_full)")
+            if key in ("backend", "backend_extra_args", "learn_amax", "trt_high_precision_dtype", "pass_through_bwd"):
                 raise MoquantUnsupported(f"quantizer attribute {key!r} is outside this path")
             assert key in self._PARTIAL_KEYS, f"{key} is not a valid `TensorQuantizer` attribute"
         d = self.__dict__
@@ -233,6 +277,19 @@ class TensorQuantizer(nn.Module):
     block_sizes = property(lambda self: self._block_sizes)
     fake_quant = property(lambda self: self._fake_quant)
     is_enabled = property(lambda self: not self._disabled)
+
+    # rotation (tensor_quantizer.py:615-669)
+    rotate_is_enabled = property(lambda self: self._rotate.enable)
+    rotate_is_fp32 = property(lambda self: self._rotate.rotate_fp32 if self._rotate.enable else False)
+    rotate_block_size = property(lambda self: self._rotate.block_size if self._rotate.enable else None)
+    rotate_back_is_enabled = property(lambda self: self._rotate.enable and self._rotate.mode == "rotate_back")
+
+    def disable_rotate(self):
+        """After a fold the rotation is baked into the weight and must not be applied again (:651-662).  Idempotent."""
+        self.__dict__["_rotate"] = replace(self._rotate, enable=False)
+
+    def _rotate_inputs(self, inputs):
+        return ops.hadamard(inputs, self.rotate_block_size)
 
     @property
     def axis(self):
@@ -452,6 +509,7 @@ class TensorQuantizer(nn.Module):
         unchanged tensor are pass-throughs until the calibration ends (disable_calib / reset_amax).  Only running-max
         calibrators qualify (a histogram would count the weight once per forward in the reference)."""
         if (type(self._calibrator).__name__ == "MaxCalibrator" and self.pre_quant_scale is None and self._bias is None
+                and not self._rotate.enable  # (a rotating quantizer returns the ROTATED weight from every call)
                 and not weight.is_inference()):  # (an inference tensor has no version counter to recognise it unchanged by)
             self._weight_stats_done = (weight.data_ptr(), weight._version, tuple(weight.shape))
 
@@ -743,23 +801,80 @@ class TensorQuantizer(nn.Module):
     # weight quantizers whose statistics weight_only_quantize already took), each through nn.Module.__call__ and the chain of
     # tests in forward() -- ~0.1 s of host time in a loop the host barely keeps ahead of the GPU (profiles/r05g_fp8_flow_overhead.md)
     def hands_back(self) -> bool:
-        """True when calling this quantizer cannot do anything to its input: disabled, no smoothing scale, and nobody
-        hooked its call.  (The reference's forward returns the input of a disabled quantizer after the pre_quant_scale
+        """True when calling this quantizer cannot do anything to its input: disabled, no rotation, no smoothing scale, and
+        nobody hooked its call.  (The reference's forward returns the input of a disabled quantizer after the pre_quant_scale
         step, tensor_quantizer.py:1119-1150.)"""
-        return (self._disabled and "_pre_quant_scale" not in self._buffers and not self._forward_hooks
+        return (self._disabled and not self._rotate.enable and "_pre_quant_scale" not in self._buffers and not self._forward_hooks
                 and not self._forward_pre_hooks and not _GLOBAL_FORWARD_HOOKS and not _GLOBAL_FORWARD_PRE_HOOKS)
 
     def weight_already_counted(self, w) -> bool:
         """True inside max_calibrate's forward loop for the weight whose statistics this calibration already holds (the
         second test of forward(), without the call)."""
         done = self._weight_stats_done
-        return (done is not None and self._if_calib and not self._if_quant and not self._disabled and done[0] == w.data_ptr()
+        return (done is not None and not self._rotate.enable and self._if_calib and not self._if_quant and not self._disabled
+                and done[0] == w.data_ptr()
                 and not w.is_inference() and done[1] == w._version and done[2] == tuple(w.shape) and not self._forward_hooks
                 and not self._forward_pre_hooks and not _GLOBAL_FORWARD_HOOKS and not _GLOBAL_FORWARD_PRE_HOOKS)
+
+    def _forward_rotated(self, inputs):
+        """forward() of a quantizer that rotates, in the reference's order (tensor_quantizer.py:1142-1219): pre_quant_scale,
+        rotate, (disabled: rotate back if asked, return), block reshape, collect, fake quant, reshape back, rotate back.
+        None of forward()'s shortcuts applies: each of them would return or quantize the UNROTATED tensor.  Two of the
+        combinations are one launch: per-tensor max calibration (the rotation with the calibrator's running abs-max
+        fused, moq_hadamard) and dynamic-block fake quantization (moq_hadamard_mx_qdq)."""
+        pqs = self.pre_quant_scale
+        if pqs is not None:
+            inputs = ops.scale_cols(inputs, pqs) if pqs.numel() == inputs.shape[-1] and pqs.numel() > 1 else inputs * pqs
+        back = self.rotate_back_is_enabled
+        if back and self._if_quant and not self._fake_quant:
+            raise ValueError("rotate_back mode is only supported with fake_quant=True.")
+        if self._disabled:
+            inputs = self._rotate_inputs(inputs)
+            return self._rotate_inputs(inputs) if back else inputs
+        collecting = self._if_calib and not self._dynamic
+        plain_layout = (self._block_sizes is None or self._block_dynamic) and self._axis is None and self._bias is None
+        cal = self._calibrator
+        if collecting and not self._if_quant and plain_layout and type(cal) is MaxCalibrator and not cal._track_amax:
+            # calibration mode: what comes back IS the rotated tensor (rotated twice under rotate_back), as in the reference
+            if cal._buf is None:
+                cal._buf = torch.zeros(1, dtype=torch.float32, device=inputs.device)
+                cal._shape, cal._dtype = (), inputs.dtype
+            elif cal._shape != ():
+                raise RuntimeError("amax shape changed!")
+            outputs = ops.hadamard(inputs, self.rotate_block_size, running_amax=cal._buf)
+            return self._rotate_inputs(outputs) if back else outputs
+        if (self._if_quant and not collecting and self._block_dynamic and plain_layout
+                and (self.is_mx_format or self._use_constant_amax or hasattr(self, "_amax"))):
+            # (without a calibrated amax the tensor-wide amax of a two-level format is that of the rotated tensor, which
+            # has to exist first: the general path below)
+            g = self._block_sizes.get(-1, None) or self._block_sizes.get(inputs.dim() - 1, None)
+            if g is None:
+                raise ValueError("block size for dynamic quantization not found.")
+            sb = self._block_sizes.get("scale_bits", None)
+            assert isinstance(sb, (tuple, list)) and len(sb) == 2
+            nb = self._num_bits if not isinstance(self._num_bits, list) else tuple(self._num_bits)
+            return ops.hadamard_block_quant(inputs, self.rotate_block_size, g, None if self.is_mx_format else self._get_amax(inputs),
+                                            nb, tuple(sb), rotate_back=back)
+        inputs = self._rotate_inputs(inputs)
+        if self._block_sizes is not None and self._fake_quant:
+            self._block_sizes_to_axis(inputs)
+        if self.is_static_block_quant:
+            self._setup_for_blockquant(inputs)
+            inputs = self._process_for_blockquant(inputs)
+        outputs = inputs
+        if collecting:
+            self.collect(inputs)
+        if self._if_quant:
+            outputs = self._fake_quantize(inputs)
+        if self.is_static_block_quant:
+            outputs = self._reset_to_original_shape(outputs)
+        return self._rotate_inputs(outputs) if back else outputs
 
     def forward(self, inputs):
         if inputs.numel() == 0:
             return inputs
+        if self._rotate.enable:
+            return self._forward_rotated(inputs)
         if (self._if_calib and not self._if_quant and not self._disabled and not self._dynamic and self._block_sizes is None
                 and self._axis is None and self._bias is None and self._weight_stats_done is None and "_pre_quant_scale" not in self._buffers
                 and type(self._calibrator) is MaxCalibrator and self._calibrator.collect_per_tensor_fast(inputs)):
@@ -841,8 +956,12 @@ class TensorQuantizer(nn.Module):
         the quant / calib switches."""
         pqs = self.pre_quant_scale
         smoothing = f" pre_quant_scale={self._short_tensor(pqs)}" if pqs is not None else ""
+        rotation = " rotated" if self.rotate_is_enabled else ""  # (_rotation_extra_repr, :1249-1255)
+        rotation += " (rotate_back)" if self.rotate_back_is_enabled else ""
+        rotation += " (fp32)" if self.rotate_is_fp32 else ""
+        rotation += f" (block={self.rotate_block_size})" if self.rotate_block_size is not None else ""
         if self._disabled:
-            return "disabled" + smoothing
+            return "disabled" + smoothing + rotation
         s = f"{'unsigned ' if self._unsigned else ''}{self._num_bits} bit"
         s += " narrow" if self._narrow_range else ""
         s += " fake" if self._fake_quant else ""
@@ -850,7 +969,7 @@ class TensorQuantizer(nn.Module):
             s += f" block_sizes={self._block_sizes},"
         else:
             s += f" axis={self._axis}" if self._axis is not None else " per-tensor"
-        s += f" amax={self._short_amax()}" + smoothing
+        s += f" amax={self._short_amax()}" + smoothing + rotation
         s += f" calibrator={type(self._calibrator).__name__}" if self._calibrator is not None else ""
         if self._bias:
             s += f" bias={self._bias}"

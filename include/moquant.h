@@ -256,6 +256,19 @@ int moq_hist_percentile(const void* hist, int elem_bytes, int64_t rows, int64_t 
 int moq_int8_pack_rows(const void* w, const float* scale, int8_t* out, int64_t rows, int64_t cols, int dt,
                        void* stream);
 
+/* INT8QTensor.quantize / dequantize (quantization/qtensor/int8_tensor.py:88, :124), arithmetic in the STORAGE dtype dt:
+ *   pack:   out[i] = (int8) clamp(rint( dt( x[i] / scale ) ), -128, 127)  -- the quotient is rounded to dt first, ties of the
+ *           rounded quotient go to even, a NaN gives 0;
+ *   unpack: out[i] = dt( q[i] * scale ).
+ * scales have dtype dt; amax_mode MOQ_AMAX_SCALAR: scales[0]; MOQ_AMAX_AXIS: scales[(i / inner) % axis_size] -- one axis of
+ * a contiguous [outer, axis, inner] view (per-channel rows: inner = Cin), last-axis blocks: inner = block, axis_size =
+ * n / block.  Any n; no alignment needed (4 elements per lane where n, inner and the pointers allow).
+ * moq_int8_pack_rows above is the exporter's fp32-quotient rule and a different function. */
+int moq_int8_pack(const void* x, const void* scales, int8_t* out, int64_t n, int dt, int amax_mode, int64_t axis_size,
+                  int64_t inner, void* stream);
+int moq_int8_unpack(const int8_t* q, const void* scales, void* out, int64_t n, int dt, int amax_mode, int64_t axis_size,
+                    int64_t inner, void* stream);
+
 /* ------------------------------------------------------------------ fused input-quantizer pass (8f-3) */
 
 /* TensorQuantizer.forward for a per-tensor input quantizer in ONE read of the activation x[rows, cols]
@@ -559,6 +572,21 @@ int moq_nvfp4_pack(const void* x, const float* amax, const float* global_amax, c
  * value of nibble 8 being +0.  packed 4-byte, out 16-byte aligned. */
 int moq_nvfp4_unpack(const uint8_t* packed, const uint8_t* scale_e4m3, const float* scale_2, void* out, int64_t n_blocks,
                      int block, int dt, void* stream);
+
+/* ------------------------------------------------------------------ fused small-batch linear on packed weights */
+
+/* Weight formats of moq_wq_linear. */
+typedef enum moq_wq_format { MOQ_WQ_INT4 = 0, MOQ_WQ_NVFP4 = 1 } moq_wq_format;
+
+/* y[t, n] = x[t, k] . W^[n, k]^T (+ bias[n]) for 1 <= t <= 32 tokens, x / y / bias in dt = MOQ_BF16 or MOQ_F16, W^ the
+ * weight the unpack kernels would write, decoded in registers and never stored:
+ *   MOQ_WQ_INT4:  packed = moq_int4_pack bytes [n, k / 2], scales dtype dt [n * k / g], g % 32 == 0, k % g == 0, scale_2 unused;
+ *   MOQ_WQ_NVFP4: packed = moq_nvfp4_pack bytes [n, k / 2], scales = E4M3 bytes [n, k / 16], scale_2 one fp32, g = 16.
+ * Every decoded weight is bit-identical to moq_int4_unpack / moq_nvfp4_unpack in dt; products are exact in fp32, sums are
+ * fp32 in a fixed order (the same bits every run), bias is added in fp32, one rounding to dt.  k % 32 == 0; any n; x and
+ * packed 16-byte aligned.  t > 32, another k or g, fp32: MOQ_ERR_UNSUPPORTED (the caller takes the unpack route). */
+int moq_wq_linear(const void* x, const uint8_t* packed, const void* scales, const float* scale_2, const void* bias, void* y,
+                  int64_t t, int64_t n, int64_t k, int g, int fmt, int dt, void* stream);
 
 /* ------------------------------------------------------------------ NVFP4 activation headroom calibration */
 

@@ -12,7 +12,8 @@ libmoquant.so (include/moquant.h).  Mirrors the reference's plugin surface for t
   hf_experts       per-expert weight quantizers on fused 3-D MoE expert containers (Mixtral, Qwen-MoE, ...)
   sparsity         create_asp_mask (2:4 magnitude), SparseGPT
   gptq             GPTQ weight update (Hessian on the matrix cores, one kernel per column block)
-  qtensor          INT4QTensor / FP8QTensor / MXFP4QTensor real quantisation (pack / unpack kernels)
+  qtensor          INT4 / INT8 / FP8 / MXFP4 / MXFP8 / NVFP4 QTensors (pack / unpack kernels), QTensorWrapper
+  compress         compress(): a calibrated model with its linear weights kept packed (RealQuantLinear), is_real_quantized
   layerwise        layer-by-layer calibration with checkpoint / resume
   export           resmooth / layernorm fusion / INT4 nibble packing of the checkpoint export (byte-identical)
   distributed      bucketed all-reduce of amax / histograms / AWQ statistics (RCCL via torch.distributed)
@@ -48,9 +49,10 @@ from .model_quant import (calibrate, disable_quantizer, enable_quantizer, fold_w
                           print_quant_summary, quantize, set_quantizer_attribute, set_quantizer_attributes_full,
                           set_quantizer_attributes_partial, set_quantizer_by_cfg, set_quantizer_by_cfg_context)
 from .tensor_quantizer import QuantizerAttributeConfig, TensorQuantizer  # noqa: F401
+from .compress import compress, is_real_quantized  # noqa: F401,E402
 
 __all__ = ["ops", "multi_tensor", "calib", "tensor_quantizer", "nn", "hf_attention", "hf_experts", "distributed", "model_calib", "model_quant",
-           "sparsity", "gptq", "export", "qtensor", "layerwise", "modelopt_plugin", "quantize", "calibrate", "fold_weight", "postprocess_amax", "disable_quantizer", "enable_quantizer",
+           "sparsity", "gptq", "export", "qtensor", "layerwise", "modelopt_plugin", "quantize", "calibrate", "compress", "is_real_quantized", "fold_weight", "postprocess_amax", "disable_quantizer", "enable_quantizer",
            "print_quant_summary", "set_quantizer_by_cfg", "set_quantizer_by_cfg_context", "set_quantizer_attributes_partial",
            "set_quantizer_attributes_full", "set_quantizer_attribute", "TensorQuantizer", "QuantizerAttributeConfig",
            "MoquantError", "MoquantUnsupported"]

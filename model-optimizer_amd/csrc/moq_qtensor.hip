@@ -975,3 +975,109 @@ extern "C" int moq_fp8_unpack_tile(const uint8_t* q, const void* scales, void* o
                                             S(stream), q, scales, out, rows, cols, br, bc, log2_or_neg(bc), cols / bc));
   return check_launch("moq_fp8_unpack_tile");
 }
+
+// ---------------------------------------------------------------- INT8QTensor pack / unpack (qtensor/int8_tensor.py:88, :124)
+// The reference's arithmetic runs in the STORAGE dtype: the quotient x / scale (scale in the tensor dtype) is rounded to the
+// dtype before the round-half-even, and the dequantized product int8 * scale is rounded once to the dtype.  Scale of element
+// i: scales[0], or scales[(i / inner) % axis_size] -- one axis of a contiguous [outer, axis, inner] view, last-axis blocks
+// being inner = block, axis_size = n / block.  V elements per lane (one 4-byte store / load of the int8 side) when n and inner
+// allow it, else one: the 7 x 48 and 1 x 16 tensors of the tests and any odd row take the same body.
+namespace moq {
+__device__ __forceinline__ int int8_of_quotient(float q) {
+  // torch: round() then clamp() keep a NaN, whose cast to int8 gives 0 on the host
+  const float t = __builtin_fminf(__builtin_fmaxf(__builtin_rintf(q), -128.0f), 127.0f);
+  return (q != q) ? 0 : (int)t;
+}
+
+template <int DT, int V, bool AXIS>
+__global__ __launch_bounds__(kBlock) void int8_pack_kernel(const void* __restrict__ x, const void* __restrict__ scales,
+                                                           int8_t* __restrict__ out, int64_t n, int64_t axis_size,
+                                                           int64_t inner) {
+  const int64_t step = (int64_t)gridDim.x * kBlock * V;
+  for (int64_t e = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * V; e < n; e += step) {
+    const float sc = load1<DT>(scales, AXIS ? (e / inner) % axis_size : 0);  // V divides inner: one scale per lane step
+    uint32_t b = 0;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const int q = int8_of_quotient(round_to_dtype<DT>(load1<DT>(x, e + i) / sc));
+      if constexpr (V == 1) out[e] = (int8_t)q;
+      b |= ((uint32_t)q & 0xFFu) << (8 * i);
+    }
+    if constexpr (V == 4) *reinterpret_cast<uint32_t*>(out + e) = b;
+  }
+}
+
+template <int DT, int V, bool AXIS>
+__global__ __launch_bounds__(kBlock) void int8_unpack_kernel(const int8_t* __restrict__ q, const void* __restrict__ scales,
+                                                             void* __restrict__ out, int64_t n, int64_t axis_size,
+                                                             int64_t inner) {
+  const int64_t step = (int64_t)gridDim.x * kBlock * V;
+  for (int64_t e = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * V; e < n; e += step) {
+    const float sc = load1<DT>(scales, AXIS ? (e / inner) % axis_size : 0);
+    uint32_t b;
+    if constexpr (V == 4) b = *reinterpret_cast<const uint32_t*>(q + e);
+    else b = (uint8_t)q[e];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      // an int8 is exact in every storage dtype; the fp32 product of two dtype values rounded once IS the dtype's product
+      const float v = (float)(int8_t)((b >> (8 * i)) & 0xFFu);
+      store1<DT>(out, e + i, v * sc);
+    }
+  }
+}
+
+static int int8_args_ok(const char* who, const void* a, const void* b, const void* c, int64_t n, int dt, int amax_mode,
+                        int64_t axis_size, int64_t inner) {
+  if (n < 0 || (n > 0 && (a == nullptr || b == nullptr || c == nullptr))) {
+    set_error("%s: null pointer or negative size", who);
+    return MOQ_ERR_INVALID;
+  }
+  if (dt != MOQ_F32 && dt != MOQ_F16 && dt != MOQ_BF16) {
+    set_error("%s: unknown dtype %d", who, dt);
+    return MOQ_ERR_INVALID;
+  }
+  if (amax_mode != MOQ_AMAX_SCALAR && amax_mode != MOQ_AMAX_AXIS) {
+    set_error("%s: unknown amax_mode %d", who, amax_mode);
+    return MOQ_ERR_INVALID;
+  }
+  if (amax_mode == MOQ_AMAX_AXIS && (axis_size <= 0 || inner <= 0)) {
+    set_error("%s: axis mode needs axis_size > 0 and inner > 0", who);
+    return MOQ_ERR_INVALID;
+  }
+  return MOQ_OK;
+}
+}  // namespace moq
+
+#define MOQ_INT8_LAUNCH(KERNEL, WHO, A, B, C)                                                                              \
+  const bool axis = amax_mode == MOQ_AMAX_AXIS;                                                                            \
+  const bool v4 = n % 4 == 0 && (!axis || inner % 4 == 0) && (reinterpret_cast<uintptr_t>(A) & 3u) == 0 &&                 \
+                  (reinterpret_cast<uintptr_t>(C) & 3u) == 0;                                                              \
+  const int grid = stream_grid((int64_t)kBlock * (v4 ? 4 : 1), n);                                                         \
+  if (v4 && axis) {                                                                                                        \
+    MOQ_DISPATCH_DTYPE(dt, hipLaunchKernelGGL((KERNEL<DT, 4, true>), dim3(grid), dim3(kBlock), 0, S(stream), A, B, C, n,   \
+                                              axis_size, inner));                                                          \
+  } else if (v4) {                                                                                                         \
+    MOQ_DISPATCH_DTYPE(dt, hipLaunchKernelGGL((KERNEL<DT, 4, false>), dim3(grid), dim3(kBlock), 0, S(stream), A, B, C, n,  \
+                                              axis_size, inner));                                                          \
+  } else if (axis) {                                                                                                       \
+    MOQ_DISPATCH_DTYPE(dt, hipLaunchKernelGGL((KERNEL<DT, 1, true>), dim3(grid), dim3(kBlock), 0, S(stream), A, B, C, n,   \
+                                              axis_size, inner));                                                          \
+  } else {                                                                                                                 \
+    MOQ_DISPATCH_DTYPE(dt, hipLaunchKernelGGL((KERNEL<DT, 1, false>), dim3(grid), dim3(kBlock), 0, S(stream), A, B, C, n,  \
+                                              axis_size, inner));                                                          \
+  }                                                                                                                        \
+  return check_launch(WHO)
+
+extern "C" int moq_int8_pack(const void* x, const void* scales, int8_t* out, int64_t n, int dt, int amax_mode,
+                             int64_t axis_size, int64_t inner, void* stream) {
+  const int rc = int8_args_ok("moq_int8_pack", x, scales, out, n, dt, amax_mode, axis_size, inner);
+  if (rc != MOQ_OK || n == 0) return rc;
+  MOQ_INT8_LAUNCH(int8_pack_kernel, "moq_int8_pack", x, scales, out);
+}
+
+extern "C" int moq_int8_unpack(const int8_t* q, const void* scales, void* out, int64_t n, int dt, int amax_mode,
+                               int64_t axis_size, int64_t inner, void* stream) {
+  const int rc = int8_args_ok("moq_int8_unpack", q, scales, out, n, dt, amax_mode, axis_size, inner);
+  if (rc != MOQ_OK || n == 0) return rc;
+  MOQ_INT8_LAUNCH(int8_unpack_kernel, "moq_int8_unpack", q, scales, out);
+}

@@ -607,6 +607,14 @@ def export_quantized_weight(module, dtype: torch.dtype):
     return out
 
 
+def _refuse_compressed(model) -> None:
+    from .qtensor import QTensorWrapper
+
+    if any(isinstance(p, QTensorWrapper) for p in model.parameters()):
+        raise NotImplementedError("checkpoint export of a model compressed by compress() (packed QTensorWrapper weights) is not "
+                                  "implemented: export the fake-quantized model (quantize + export_hf_checkpoint) instead")
+
+
 @torch.no_grad()
 def export_state_dict(model, dtype: torch.dtype, dummy_forward_fn=None, shard_weights: bool | None = None) -> dict:
     """Checkpoint tensors of a quantized model: resmooth / fuse (when a probe forward is given), then pack every
@@ -620,6 +628,7 @@ def export_state_dict(model, dtype: torch.dtype, dummy_forward_fn=None, shard_we
     from . import distributed as mdist
     from .model_calib import refuse_rotation
 
+    _refuse_compressed(model)
     refuse_rotation(model, "checkpoint export")  # (the packers read weights and amax, not the quantizer's forward)
     if dummy_forward_fn is not None:
         requantize_resmooth_fused_llm_layers(model, dummy_forward_fn)
@@ -983,6 +992,7 @@ def export_hf_checkpoint(model, dtype: torch.dtype | None = None, export_dir: st
     Returns the hf_quant_config dict."""
     import tempfile
 
+    _refuse_compressed(model)
     export_dir = export_dir or tempfile.gettempdir()
     os.makedirs(export_dir, exist_ok=True)
     param = next(model.parameters())

@@ -9,6 +9,7 @@ tiny host-side bookkeeping only; every pass over tensor data is one of our kerne
 from __future__ import annotations
 
 import ctypes
+import math
 from contextlib import contextmanager
 
 import torch
@@ -709,6 +710,92 @@ def pack_int4_in_uint8(weight: torch.Tensor, weights_scaling_factor: torch.Tenso
             check(_lib.lib().moq_int4_pack_export(_p(w3[b]), _p(s3[b]), _p(o3[b]), out_dim, in_dim, int(g),
                                                   _dt(w), stream))
     return out
+
+
+# ----------------------------------------------------------------------------------------------- real INT8
+def _int8_layout(shape, sshape):
+    """(mode, axis_size, inner) of INT8QTensor scales over a contiguous tensor of `shape`: one scale; keepdims scales of ONE
+    run of adjacent kept dims ([rows, 1] of axis 0: a contiguous [outer, axis, inner] view); or last-axis blocks
+    ([..., K / block])."""
+    n, ns = math.prod(shape), math.prod(sshape)
+    if ns == 1:
+        return _lib.AMAX_SCALAR, 1, 1
+    shape, sshape = tuple(shape), tuple(sshape)
+    if len(sshape) == len(shape):
+        if sshape[:-1] == shape[:-1] and sshape[-1] and shape[-1] % sshape[-1] == 0 and sshape[-1] != 1:
+            return _lib.AMAX_AXIS, ns, shape[-1] // sshape[-1]  # blocks along the last dim, row-major
+        kept = [d for d in range(len(shape)) if sshape[d] != 1]
+        if all(sshape[d] == shape[d] for d in kept) and kept == list(range(kept[0], kept[-1] + 1)):
+            return _lib.AMAX_AXIS, ns, math.prod(shape[kept[-1] + 1:])
+    raise MoquantUnsupported(f"INT8 scales of shape {sshape} over a tensor of shape {shape}: per-tensor, one axis or last-axis "
+                             "blocks only")
+
+
+@torch.no_grad()
+def int8_quantize(inputs: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(inputs / expanded scales).round().clamp(-128, 127).to(int8) in the tensor dtype -- INT8QTensor.quantize's last
+    line (int8_tensor.py:88), one kernel."""
+    _require_gpu(inputs, "int8_quantize")
+    x = inputs.detach().contiguous()
+    s = scales.detach().to(device=x.device, dtype=x.dtype).contiguous()
+    mode, axis_size, inner = _int8_layout(x.shape, s.shape)
+    out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+    with _on(x) as stream:
+        check(_lib.lib().moq_int8_pack(_p(x), _p(s), _p(out), x.numel(), _dt(x), mode, axis_size, inner, stream))
+    return out
+
+
+@torch.no_grad()
+def int8_dequantize(quantized: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """quantized.to(dtype) * expanded scales.to(dtype) -- INT8QTensor.dequantize (int8_tensor.py:124)."""
+    _require_gpu(quantized, "int8_dequantize")
+    q = quantized.detach().contiguous().view(torch.int8)
+    s = scales.detach().to(device=q.device, dtype=dtype).contiguous()
+    mode, axis_size, inner = _int8_layout(q.shape, s.shape)
+    out = torch.empty(q.shape, dtype=dtype, device=q.device)
+    with _on(q) as stream:
+        check(_lib.lib().moq_int8_unpack(_p(q), _p(s), _p(out), q.numel(), _dt(out), mode, axis_size, inner, stream))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- fused linear on packed weights
+WQ_INT4, WQ_NVFP4 = 0, 1
+
+
+@torch.no_grad()
+def wq_linear(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor, scale_2: torch.Tensor | None,
+              bias: torch.Tensor | None, group: int, fmt: int) -> torch.Tensor:
+    """F.linear(x, W^, bias) for at most 32 tokens with W^ = the weight moq_int4_unpack (fmt WQ_INT4: `scales` in x's dtype, one
+    per `group` elements) or moq_nvfp4_unpack (WQ_NVFP4: float8_e4m3fn block scales, fp32 `scale_2`, group 16) would write from
+    `packed` [N, K / 2] -- decoded in registers by one weight-streaming kernel, never stored.  x: [..., K] bf16 / f16.  Raises
+    MoquantUnsupported for a shape the kernel does not take (more than 32 tokens, K % 32, INT4 groups that 32 does not divide)."""
+    _require_gpu(x, "wq_linear")
+    k = x.shape[-1]
+    x2 = x.detach().reshape(-1, k).contiguous()
+    n = packed.shape[0]
+    if packed.dim() != 2 or packed.shape[1] * 2 != k or packed.dtype != torch.uint8:
+        raise MoquantError(f"wq_linear: packed weight {tuple(packed.shape)} {packed.dtype} does not fit x [..., {k}]")
+    p = packed.detach().contiguous()
+    if fmt == WQ_INT4:
+        s = scales.detach().contiguous()
+        if s.dtype != x2.dtype or s.numel() * int(group) != n * k:
+            raise MoquantUnsupported("wq_linear: INT4 scales must have x's dtype, one per group")
+        s2 = None
+    else:
+        s = scales.detach().contiguous().view(torch.uint8)
+        if scales.dtype != torch.float8_e4m3fn or s.numel() * 16 != n * k or scale_2 is None:
+            raise MoquantUnsupported("wq_linear: NVFP4 needs float8_e4m3fn block scales [N, K / 16] and scale_2")
+        s2 = _f32(scale_2, x2.device).reshape(-1)[:1]
+    b = None
+    if bias is not None:
+        if bias.dtype != x2.dtype or bias.numel() != n:
+            raise MoquantUnsupported("wq_linear: bias must have x's dtype and one entry per output")
+        b = bias.detach().contiguous()
+    y = torch.empty(x2.shape[0], n, dtype=x2.dtype, device=x2.device)
+    with _on(x2) as stream:
+        check(_lib.lib().moq_wq_linear(_p(x2), _p(p), _p(s), _p(s2), _p(b), _p(y), x2.shape[0], n, k, int(group), int(fmt),
+                                       _dt(x2), stream))
+    return y.reshape(*x.shape[:-1], n)
 
 
 # ----------------------------------------------------------------------------------------------- AWQ / smooth

@@ -1,5 +1,6 @@
 """Real-quantised tensors of the path -- mirrors of modelopt.torch.quantization.qtensor.{INT4QTensor, FP8QTensor,
-MXFP4QTensor} (qtensor/int4_tensor.py:39-130, fp8_tensor.py:40-151, mxfp4_tensor.py:37-144): same classmethod
+MXFP4QTensor, INT8QTensor} (qtensor/int4_tensor.py:39-130, fp8_tensor.py:40-151, mxfp4_tensor.py:37-144,
+int8_tensor.py:35-124) and of QTensorWrapper / pack_real_quantize_weight (qtensor/base_qtensor.py:96-238): same classmethod
 `quantize(...) -> (qtensor, scales)` and `dequantize(dtype, scale=..., block_sizes=...)` surface, every pass over
 tensor data is one HIP kernel (block amax, pack, unpack).  GPU tensors only."""
 
@@ -23,13 +24,17 @@ class BaseQuantizedTensor:
 
 
 def _div448(amax: torch.Tensor) -> torch.Tensor:
-    """amax / 448.0.  torch's GPU `tensor / python_float` multiplies by the reciprocal, which is one ulp off the CPU result
+    return _div_const(amax, 448.0)
+
+
+def _div_const(amax: torch.Tensor, c: float) -> torch.Tensor:
+    """amax / c (c = 448.0, 127.0).  torch's GPU `tensor / python_float` multiplies by the reciprocal, which is one ulp off the CPU result
     for some inputs (tensor / tensor divides on both devices).  numerics "host" (default): the TRUE division = the
     reference's CPU run, whatever the device; "device": torch's own kernel on the tensor's device = the reference's run
     there (numerics.py; tools/ops_fuzz.py compares that mode with the reference on the GPU)."""
     if numerics.on_host() or not amax.is_cuda:
-        return amax / torch.full((), 448.0, dtype=amax.dtype, device=amax.device)
-    return amax / 448.0
+        return amax / torch.full((), c, dtype=amax.dtype, device=amax.device)
+    return amax / c
 
 
 def _pad_last(x: torch.Tensor, block: int) -> torch.Tensor:
@@ -39,15 +44,16 @@ def _pad_last(x: torch.Tensor, block: int) -> torch.Tensor:
 
 class INT4QTensor(BaseQuantizedTensor):
     @classmethod
-    def quantize(cls, input: torch.Tensor, block_size: int):
+    def quantize(cls, input: torch.Tensor, block_size: int, rounding: int = _lib.ROUND_HALF_AWAY):
         """int4_tensor.py:39-87: flat view padded to a block multiple, scales = 7 / block amax (input dtype),
         byte = ((q_even + 8) << 4) | (q_odd + 8).  Rounding follows the reference's CUDA kernel (the path taken
-        for GPU tensors there): clamp, then round-half-away of v + 8 (tensor_quant_gpu.cu:322-333)."""
+        for GPU tensors there): clamp, then round-half-away of v + 8 (tensor_quant_gpu.cu:322-333); ROUND_HALF_EVEN is
+        its eager twin (:69-84), what the reference's CPU run computes."""
         assert input.shape[-1] % 2 == 0, "Input tensor must have even number on last dimension."
         flat = _pad_last(input.reshape(-1), block_size).contiguous()
         amax = ops.reduce_amax(flat.view(-1, block_size), axis=(1,))  # input dtype, [n/g, 1]
         scales = (7.0 / amax).view(-1, 1)
-        packed = ops.int4_quantize(flat, scales.reshape(-1), block_size, rounding=_lib.ROUND_HALF_AWAY)
+        packed = ops.int4_quantize(flat, scales.reshape(-1), block_size, rounding=rounding)
         packed = packed.reshape(*input.shape[:-1], -1)
         return cls(input.shape, input.dtype, packed), scales
 
@@ -340,3 +346,143 @@ class NVFP4QTensor(BaseQuantizedTensor):
         out = ops.nvfp4_dequantize(self._quantized_data, scale, kwarg["double_scale"], dtype, kwarg["block_sizes"][-1])
         shape = self.metadata["shape"]
         return out[..., : shape[-1]].reshape(shape)
+
+
+class INT8QTensor(BaseQuantizedTensor):
+    """int8 elements under scales of the storage dtype (qtensor/int8_tensor.py:28-124): per-tensor, one kept axis, or blocks
+    along the last dim.  One pass each way (`moq_int8_pack` / `moq_int8_unpack`); the arithmetic is the reference's, in
+    the storage dtype: scales = amax / 127 in the input dtype, the quotient rounded to it before the round-half-even."""
+
+    @staticmethod
+    def _last_block(input: torch.Tensor, block_sizes: dict) -> int:
+        dims = {(d if d >= 0 else input.dim() + d): b for d, b in block_sizes.items() if isinstance(d, int)}
+        if list(dims) != [input.dim() - 1]:
+            raise MoquantUnsupported("INT8QTensor: blocks along the last dim only (reference N-D blocks: int8_tensor.py:68-85)")
+        return dims[input.dim() - 1]
+
+    @classmethod
+    def quantize(cls, input: torch.Tensor, scales: torch.Tensor | None = None, axis=None, block_sizes: dict | None = None):
+        """int8_tensor.py:35-90: (INT8QTensor, scales).  With blocks the data keeps the zero padding of a ragged last dim
+        (the reference pads only when it computes the scales itself); dequantize crops it."""
+        x = input
+        if block_sizes:
+            block = cls._last_block(input, block_sizes)
+            if scales is None:
+                x = _pad_last(input, block).contiguous()
+                scales = _div_const(ops.reduce_block_amax(x, {-1: block}), 127.0)
+            assert x.shape[-1] % block == 0, f"Tensor dimension {x.dim() - 1}, {x.shape[-1]} is not divisible by {block}."
+            expected = (*x.shape[:-1], x.shape[-1] // block)
+            assert tuple(scales.shape) == expected, f"Mismatch in expected scale shape: {scales.shape} vs {expected}"
+        elif scales is None:
+            if axis is None:
+                scales = _div_const(ops.reduce_amax(x), 127.0)
+            else:
+                ax = [axis] if isinstance(axis, int) else list(axis)
+                reduce_axis = [i for i in range(x.dim()) if i not in ax and (i - x.dim()) not in ax]
+                scales = _div_const(ops.reduce_amax(x, axis=reduce_axis), 127.0)
+        return cls(input.shape, input.dtype, ops.int8_quantize(x, scales)), scales
+
+    def dequantize(self, dtype: torch.dtype = None, **kwarg):
+        """int8_tensor.py:92-124."""
+        dtype = dtype or self.metadata["dtype"]
+        assert "scale" in kwarg, "Require scale for INT8 dequantization."
+        scales, block_sizes = kwarg["scale"], kwarg.get("block_sizes")
+        q = self._quantized_data
+        if block_sizes:
+            block = self._last_block(q, block_sizes)
+            assert q.shape[-1] % block == 0, f"Dimension {q.shape[-1]} is not divisible by {block}."
+            expected = (*q.shape[:-1], q.shape[-1] // block)
+            assert tuple(scales.shape) == expected, f"Scales shape {scales.shape} must match expected {expected}."
+        out = ops.int8_dequantize(q, scales, dtype)
+        return out[tuple(slice(0, d) for d in self.metadata["shape"])]
+
+
+class QTensorWrapper(torch.nn.Parameter):
+    """A packed weight as an nn.Parameter (the interface of qtensor/base_qtensor.py:96-145): `.data` is the packed storage,
+    `metadata` the original shape and dtype and the QTensor class that reads it.  Built from a QTensor, or from packed storage
+    plus the metadata of the wrapper it replaces."""
+
+    _META_KEYS = ("qtensor_class", "shape", "dtype")
+
+    def __new__(cls, qtensor, metadata: dict | None = None):
+        storage = qtensor
+        if isinstance(qtensor, BaseQuantizedTensor):
+            storage = qtensor._quantized_data
+            if metadata is None:
+                metadata = {**qtensor.metadata, "qtensor_class": type(qtensor)}
+        missing = [k for k in cls._META_KEYS if k not in (metadata or {})]
+        assert not missing, f"metadata: {metadata} lacks {missing}"
+        wrapper = super().__new__(cls, storage, requires_grad=False)
+        wrapper.metadata = metadata
+        return wrapper
+
+    def _qtensor_as(self, dtype):
+        meta = self.metadata
+        return meta["qtensor_class"](meta["shape"], dtype, self.data)
+
+    def dim(self):
+        """The rank of the ORIGINAL weight (what module code asks a weight for), not of the packed storage."""
+        return len(self.metadata["shape"])
+
+    def to(self, *args, **kwargs):
+        """Moves the packed bytes; a dtype only changes what the weight dequantizes to."""
+        device, dtype = torch._C._nn._parse_to(*args, **kwargs)[:2]
+        if device is not None:
+            self.data = self.data.to(device)
+        return QTensorWrapper(self._qtensor_as(dtype or self.metadata["dtype"]))
+
+    def get_qtensor(self):
+        return self._qtensor_as(self.metadata["dtype"])
+
+    def get_state(self):
+        return {"metadata": self.metadata, "quantized_data.shape": self.data.shape, "quantized_data.dtype": self.data.dtype}
+
+
+def dynamically_update_state_methods(module):
+    """load_state_dict for a module whose weight may be a QTensorWrapper (the role of base_qtensor.py:172-202): nn.Module would
+    refuse the packed tensor for its shape and dtype, so packed entries are taken out of the incoming dict first -- copied into
+    the wrapper, or wrapped where the parameter is still on the meta device -- the module's own loader sees the rest, and the
+    entries are put back for whoever reads the dict afterwards."""
+    inherited = module._load_from_state_dict
+
+    def load_packed_first(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        packed = {}
+        for name, held in list(self._parameters.items()):
+            key = prefix + name
+            if not isinstance(held, QTensorWrapper) or key not in state_dict:
+                continue
+            packed[key] = state_dict.pop(key)
+            if held.is_meta:
+                self._parameters[name] = QTensorWrapper(packed[key], metadata=held.metadata)
+            else:
+                with torch.no_grad():
+                    held.data.copy_(packed[key])
+        inherited(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        missing_keys[:] = [k for k in missing_keys if k not in packed]  # (loaded above, not missing)
+        state_dict.update(packed)
+
+    module._load_from_state_dict = load_packed_first.__get__(module, type(module))
+
+
+def _packs_its_weight(m) -> bool:
+    w, wq = getattr(m, "weight", None), getattr(m, "weight_quantizer", None)
+    if w is None or wq is None or w.is_meta:  # nothing to pack, or nothing materialised yet
+        return False
+    return bool(wq.is_enabled and not wq._fake_quant and w.element_size() > 1)  # (one-byte storage is packed already)
+
+
+def pack_real_quantize_weight(module, force_quantize: bool = False):
+    """Replace the weight of every submodule whose weight quantizer is enabled and in real-quantize mode by its packed form
+    (the role of base_qtensor.py:205-238).  A quantizer chain packs with its first member, as in the reference; with
+    `force_quantize` a quantizer that had already packed once packs again."""
+    from .tensor_quantizer import SequentialQuantizer
+
+    with SequentialQuantizer.convert_to_single_quantizer(module), torch.no_grad():
+        for m in [m for m in module.modules() if m is not module and _packs_its_weight(m)]:
+            if force_quantize:
+                m.weight_quantizer._dequantize = False
+            m.weight = QTensorWrapper(m.weight_quantizer(m.weight))
+
+
+torch.serialization.add_safe_globals([QTensorWrapper, INT4QTensor, FP8QTensor, MXFP4QTensor, MXFP8QTensor, NVFP4QTensor,
+                                      INT8QTensor])

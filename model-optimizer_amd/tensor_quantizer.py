@@ -10,7 +10,9 @@ search inner loop), and otherwise one kernel per stage.  GPU tensors only: there
 Scope: fake quantization for INT-k (per-tensor / per-channel / static last-axis blocks), FP8-E4M3
 (per-tensor / per-channel), dynamic MX blocks, static block grids on any axes (last axis and last-two-axes tiles without a copy), and the affine
 offset (`bias`) of the KV-cache presets, and rotation (a normalized Hadamard transform of the last dim before the
-quantizer, optionally again after it).  Real-quant QTensors are outside this path and raise.
+quantizer, optionally again after it).  With fake_quant=False a quantizer packs its input once (`_real_quantize`: INT4 blocks,
+INT8, FP8, MXFP4 / MXFP8, NVFP4 -> a QTensor, the scales kept in `_scale` / `_double_scale`) and from then on dequantizes the
+QTensorWrapper it is handed (mtq.compress); NF4, four-over-six and rotating quantizers refuse that mode by name.
 """
 
 from __future__ import annotations
@@ -164,8 +166,6 @@ class TensorQuantizer(nn.Module):
                  if_calib=False, amax=None):
         super().__init__()
         cfg = quant_attribute_cfg or QuantizerAttributeConfig()
-        if not cfg.fake_quant:
-            raise MoquantUnsupported("real quantization (fake_quant=False) is outside this path")
         # plain (non-tensor, non-module) state goes straight into the instance dict: nn.Module.__setattr__ checks every
         # assignment against its parameter / buffer / module tables, and a Llama-3-8B conversion makes 800 quantizers x 28 of
         # them (half of the convert + set_quantizers stages)
@@ -188,6 +188,7 @@ class TensorQuantizer(nn.Module):
 
     # ------------------------------------------------------------------ configuration
     _rotate = RotateConfig()   # (instances made before the attribute existed, e.g. unpickled ones: no rotation)
+    _dequantize = False        # set by _real_quantize: later calls are handed the packed weight and only dequantize
     _weight_stats_done = None  # (data_ptr, version, shape) of the weight whose max statistics this calibration already holds
 
     _LAYOUT_CACHES = ("_block_reshape_size", "_padding", "_slices", "_original_shape", "_amax_shape_for_export", "_block_amax_view",
@@ -204,8 +205,6 @@ class TensorQuantizer(nn.Module):
         temporary configuration (set_quantizer_by_cfg_context) or a full re-assignment; an `_amax` whose shape no longer
         fits the new layout is refused where it is next written (`Changing shape when setting amax is not allowed`), and a
         caller that wants a clean slate calls reset_amax()."""
-        if not cfg.fake_quant:
-            raise MoquantUnsupported("real quantization (fake_quant=False) is outside this path")
         self.drop_layout_caches()
         self._take_config(cfg)
 
@@ -246,8 +245,7 @@ class TensorQuantizer(nn.Module):
                         self._calibrator._axis = None
                 layout = True
             elif key == "fake_quant":
-                if not val:
-                    raise MoquantUnsupported("real quantization (fake_quant=False) is outside this path")
+                d["_fake_quant"] = bool(val)
             elif key == "bias":
                 d["_bias"] = dict(val) if val else None
             elif key == "use_constant_amax":
@@ -725,6 +723,91 @@ class TensorQuantizer(nn.Module):
             inputs = inputs - self.bias_calibrator.compute_bias()
         self._calibrator.collect(inputs)
 
+    # ------------------------------------------------------------------ real quantization (tensor_quantizer.py:292-302, :788-888)
+    def dequantize(self, inputs):
+        """De-quantize a real quantized tensor (a QTensor or the QTensorWrapper parameter holding one)."""
+        from .qtensor import BaseQuantizedTensor, QTensorWrapper
+
+        qtensor = inputs.get_qtensor() if isinstance(inputs, QTensorWrapper) else inputs
+        assert isinstance(qtensor, BaseQuantizedTensor), "Expected input as real quantized tensors."
+        return qtensor.dequantize(scale=self._scale, block_sizes=self.block_sizes,
+                                  double_scale=getattr(self, "_double_scale", None),
+                                  scale_zeros=getattr(self, "_scale_zeros", None))
+
+    def _nb(self):
+        return tuple(self._num_bits) if isinstance(self._num_bits, (list, tuple)) else self._num_bits
+
+    def _is_real_quantize_support(self):
+        nb = self._nb()
+        return bool((nb == 4 and self._block_sizes) or (nb == (2, 1) and self._block_sizes) or nb in ((4, 3), 8))
+
+    def _set_buffer(self, key, value):
+        if hasattr(self, key):
+            setattr(self, key, value)
+        else:
+            self.register_buffer(key, value)
+
+    def _real_quantize(self, inputs):
+        """The branches of the reference's _real_quantize in its order; NF4 and four-over-six are refused where it reaches them."""
+        from . import numerics, qtensor as qt
+
+        assert self._is_real_quantize_support(), "Real quantization not supported for this format."
+        nb, bs = self._nb(), self._block_sizes
+        sb = tuple(bs["scale_bits"]) if bs and isinstance(bs.get("scale_bits"), (list, tuple)) else (bs or {}).get("scale_bits")
+        buffers = {}
+        if bs and sb == (8, 0) and bs.get("type") == "dynamic":  # MX formats first: MXFP8 is (4, 3) too
+            if nb == (2, 1):
+                outputs, buffers["_scale"] = qt.MXFP4QTensor.quantize(inputs, bs[-1])
+            elif nb == (4, 3):
+                assert bs[-1] == qt.MXFP8QTensor.BLOCK_SIZE, \
+                    f"MXFP8 requires block size {qt.MXFP8QTensor.BLOCK_SIZE}, got {bs[-1]}"
+                outputs, buffers["_scale"] = qt.MXFP8QTensor.quantize(inputs)
+            else:
+                raise ValueError(f"Unsupported MX format: num_bits={self._num_bits}. "
+                                 f"Expected (2, 1) for MXFP4 or (4, 3) for MXFP8.")
+        elif nb == (4, 3):
+            # per-tensor / per-channel: the calibrated (possibly rank-synced) amax; blocks recompute theirs (:826-828)
+            use_amax = self.amax is not None and not (bs and self.amax.numel() == 1)
+            outputs, buffers["_scale"] = qt.FP8QTensor.quantize(inputs, axis=self._axis, block_sizes=self._int_block_sizes(),
+                                                                scales=qt._div448(self.amax) if use_amax else None)
+        elif nb == 8:
+            outputs, buffers["_scale"] = qt.INT8QTensor.quantize(inputs, axis=self._axis, block_sizes=self._int_block_sizes())
+        elif (sb or 0) == 8 and bs.get("scale_block_sizes", None):
+            raise MoquantUnsupported("real quantization to NF4 (scale_bits=8 with scale_block_sizes: double quantization) is "
+                                     "outside this path")
+        elif sb == (4, 3):
+            if bs.get("four_over_six", False):
+                raise NotImplementedError(
+                    "NVFP4 Four-Over-Six (4/6) is not supported via mtq.compress: the per-block M=4/M=6 choice baked into the "
+                    "quantizer amax by MSE calibration is not preserved by real quantization. Use mtq.quantize + export for "
+                    "4/6 instead.")
+            wsf2 = qt.NVFP4QTensor.get_weights_scaling_factor_2_from_quantizer(self) if self.amax is not None else None
+            if wsf2 is not None and wsf2.numel() != 1:
+                raise MoquantUnsupported("NVFP4 real quantization: a static block amax without a global_amax gives no tensor-wide "
+                                         "scale (promote the quantizer first)")
+            outputs, buffers["_scale"], buffers["_double_scale"] = qt.NVFP4QTensor.quantize(
+                inputs, bs[-1], weights_scaling_factor_2=wsf2)
+        else:
+            # the eager twin's round-half-even is what the reference computes on CPU; its CUDA kernel rounds half away
+            rounding = qt._lib.ROUND_HALF_EVEN if numerics.on_host() else qt._lib.ROUND_HALF_AWAY
+            outputs, buffers["_scale"] = qt.INT4QTensor.quantize(inputs, bs[-1], rounding=rounding)
+        for k, v in buffers.items():
+            self._set_buffer(k, v)
+        self._dequantize = True  # called while the model's weights are compressed: later forwards only dequantize
+        return outputs
+
+    def _int_block_sizes(self):
+        """block_sizes as the QTensor classes take it: the integer (dim) keys only."""
+        bs = {k: v for k, v in (self._block_sizes or {}).items() if isinstance(k, int)}
+        return bs or None
+
+    def _quantize(self, inputs):
+        if self._fake_quant:
+            return self._fake_quantize(inputs)
+        if not self._dequantize:
+            return self._real_quantize(inputs.contiguous())
+        raise ValueError("self._dequantize is True and self.fake_quant is False. This case should have been handled.")
+
     def _fake_quantize(self, inputs):
         bias = None if self._bias is None or self._block_dynamic else self._get_bias(inputs)
         if bias is None:  # (dynamic block formats take no offset: tensor_quant.py:539-561)
@@ -769,7 +852,7 @@ class TensorQuantizer(nn.Module):
         """pre_quant_scale * x -> collect -> fake-quantize of a PER-TENSOR quantizer as ONE kernel pass over the
         activation (ops.input_quant; the reference runs a multiply, an amax + amin pair and ~8 elementwise kernels,
         tensor_quantizer.py:1143-1212).  Returns the output, or None when this call is not of that shape."""
-        if (self._disabled or self._bias is not None or inputs.dtype not in (torch.float32, torch.float16, torch.bfloat16)
+        if (self._disabled or not self._fake_quant or self._bias is not None or inputs.dtype not in (torch.float32, torch.float16, torch.bfloat16)
                 or self._axis is not None or self._block_sizes is not None or self._dynamic
                 or not (self._if_quant or self._if_calib) or pqs.numel() != inputs.shape[-1] or pqs.numel() < 2
                 or inputs.shape[-1] % (4 if inputs.dtype == torch.float32 else 8)):
@@ -828,6 +911,9 @@ class TensorQuantizer(nn.Module):
         back = self.rotate_back_is_enabled
         if back and self._if_quant and not self._fake_quant:
             raise ValueError("rotate_back mode is only supported with fake_quant=True.")
+        if not self._disabled and self._if_quant and not self._fake_quant:
+            raise MoquantUnsupported("a rotating quantizer (rotate.enable) cannot real-quantize (fake_quant=False): the packed "
+                                     "weight would be the rotated one; fold the rotation first")
         if self._disabled:
             inputs = self._rotate_inputs(inputs)
             return self._rotate_inputs(inputs) if back else inputs
@@ -871,6 +957,12 @@ class TensorQuantizer(nn.Module):
         return self._rotate_inputs(outputs) if back else outputs
 
     def forward(self, inputs):
+        if not self._fake_quant or self._dequantize:
+            from .qtensor import BaseQuantizedTensor, QTensorWrapper
+
+            if isinstance(inputs, (BaseQuantizedTensor, QTensorWrapper)):
+                assert self._dequantize, "No dequantization stats in the tensor quantizer."
+                return self.dequantize(inputs)
         if inputs.numel() == 0:
             return inputs
         if self._rotate.enable:
@@ -923,7 +1015,7 @@ class TensorQuantizer(nn.Module):
         if self._if_quant:
             # no `.contiguous()` here: every op takes what it needs (per-tensor formats walk a permuted dense
             # tensor in place, the others copy)
-            outputs = self._fake_quantize(inputs)
+            outputs = self._quantize(inputs)
         if self.is_static_block_quant:
             outputs = self._reset_to_original_shape(outputs)
         return outputs
